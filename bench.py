@@ -10,7 +10,12 @@ quotient, FRI open and proof assembly.  The executor and the event upload run be
 timed region.  Every rank proves its own replica (no data-path collective: replicas only), so
 the job is weak-scaled; `value` is the wall time of one step (max over ranks).
 
-Also reported: the HBM roofline of the coset-LDE (NTT) kernels on SURVEY 8(d)'s basis
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that figure needs: setup,
+W warm-up proofs, the N timed proofs, and the result line.  `--dump-outputs DIR` also writes
+what the last timed step returned (the proof's bytes) as DIR/<name>.npy.  Everything below runs
+only with `--full`.
+
+Also reported with `--full`: the HBM roofline of the coset-LDE (NTT) kernels on SURVEY 8(d)'s basis
 (12*n*w B per LDE / NTT kernel time, per-launch HIP events on the prover's stream), their
 VALU-issue fraction, the Poseidon2 kernels' VALU fraction, and the oracle (CPU restatement)
 proving the same headline workload on the host cores.
@@ -629,6 +634,23 @@ def timed_steps(step, steps, dist=None, sync=lambda: None):
     return ms
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the last timed step returned, one DIR/<name>.npy per array (float32
+    or float64, whole: a proof is a few MB, the pcs roots a few KB), so that two builds run
+    with the same arguments -- hence on the same inputs -- can be compared output for output."""
+    import numpy as np
+    total = sum(int(a.nbytes) for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def cold_first_proof():
     """The first proof of a fresh process: scripts/cold_first_proof.py in a
     child process -- init, setup, record, ONE prove (timed), host-verified, then two warm proofs
@@ -676,7 +698,17 @@ def run_pcs(args, rank, world, device, dist, coll):
 
     for _ in range(args.warmup):
         root, fri, fin = step()
-    ms = timed_steps(step, args.steps, dist, sync=torch.cuda.synchronize)
+    last = {}
+
+    def kept():  # the last timed step's results stay referenced for --dump-outputs
+        last["out"] = step()
+
+    ms = timed_steps(kept, args.steps, dist, sync=torch.cuda.synchronize)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        dump_outputs(args.dump_outputs,
+                     {name: np.asarray(a, dtype=np.float64)
+                      for name, a in zip(("root", "fri_roots", "fri_final"), last["out"])})
     root, fri, fin = step()  # collective: every rank takes part
     exact = None
     if world > 1 and rank == 0:
@@ -713,6 +745,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the host verification of the "
+                         "proof, the per-kernel timings and rooflines, the fresh-process first "
+                         "proof, the sustained and multi-lane rates, the shard-solo curve, the "
+                         "end-to-end / hand-over paths and the CPU baseline (the --no-* and "
+                         "--sustain-s / --solo-world / --rccl-sharded options choose among them; "
+                         "without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as "
+                         "DIR/<name>.npy (replicas / sharded: proof.npy, the proof's bytes as "
+                         "float32; pcs: root.npy, fri_roots.npy, fri_final.npy as float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cold", action="store_true",
                     help="skip the fresh-process first-proof measurement (cold_first_proof_ms)")
@@ -738,6 +781,9 @@ def main():
     ap.add_argument("--log-n", type=int, default=24, help="pcs mode: trace rows = 2^log_n")
     ap.add_argument("--cols", type=int, default=64, help="pcs mode: trace columns")
     args = ap.parse_args()
+    if not args.full:  # a plain run times the headline and nothing else
+        args.no_cpu_baseline = args.no_cold = args.no_extra = True
+        args.sustain_s, args.solo_world, args.rccl_sharded = 0.0, "", False
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -805,19 +851,27 @@ def main():
                                       ctypes.byref(plen), ctypes.byref(timings) if timings else None))
         return _lib.take_bytes(ptr, plen.value)
 
-    t_first = time.perf_counter()
-    first_proof = one()  # the first prove after setup in this process (counts as a warmup step)
-    first_ms = (time.perf_counter() - t_first) * 1e3
-    for _ in range(args.warmup - 1):  # the lane's buffer pool fills during the first proofs
-        one()
-    # one timed-with-events proof for the roofline (kept out of the headline timing), verified on
-    # the host; the warmup is repeated after it, right before the timed steps, so the GPU is not
-    # coming out of the idle (clocked-down) phase of the host verification when timing starts
-    tm = _lib.Timings()
-    proof = one(tm)
-    client.verify(sdk.BfProofWithPublicValues(proof=proof, stdin=stdin), vk)
-    for _ in range(args.warmup):
-        one()
+    tm = None
+    if args.full:
+        t_first = time.perf_counter()
+        first_proof = one()  # the first prove after setup in this process (counts as a warmup step)
+        first_ms = (time.perf_counter() - t_first) * 1e3
+        for _ in range(args.warmup - 1):  # the lane's buffer pool fills during the first proofs
+            one()
+        # one timed-with-events proof for the roofline (kept out of the headline timing), verified
+        # on the host; the warmup is repeated after it, right before the timed steps, so the GPU is
+        # not coming out of the idle (clocked-down) phase of the host verification when timing starts
+        tm = _lib.Timings()
+        proof = one(tm)
+        client.verify(sdk.BfProofWithPublicValues(proof=proof, stdin=stdin), vk)
+        for _ in range(args.warmup):
+            one()
+    else:  # exactly --warmup proofs; the first is kept to compare the last timed one with
+        first_proof = proof = None
+        for k in range(args.warmup):
+            p = one()
+            if k == 0:
+                first_proof = proof = p
 
     last = {}
 
@@ -826,10 +880,18 @@ def main():
 
     ms = timed_steps(kept, args.steps, dist, sync=lambda: _lib.check(L.bfz_synchronize()))
     # every timed step proves the same record: the last one must be the verified proof's bytes
+    # (of a plain run: the first warm-up proof's)
+    if proof is None:
+        proof = last["proof"]
     if last["proof"] != proof:
-        raise SystemExit("bench: the last timed proof differs from the verified proof")
-    if first_proof != proof:
+        raise SystemExit("bench: the last timed proof differs from the "
+                         + ("verified proof" if args.full else "first warm-up proof"))
+    if first_proof is not None and first_proof != proof:
         raise SystemExit("bench: the first proof differs from the verified proof")
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        dump_outputs(args.dump_outputs,
+                     {"proof": np.frombuffer(last["proof"], dtype=np.uint8).astype(np.float32)})
     extra = {}
     if not sharded and args.sustain_s > 0:
         last.clear()
@@ -851,7 +913,6 @@ def main():
             "error": f"no result within {SHARDED_EXTRA_LIMIT_S} s (abandoned)"}
 
     if rank == 0:
-        lde_gbs = tm.lde_bytes / (tm.lde_ms * 1e-3) / 1e9 if tm.lde_ms > 0 else 0.0
         # whole job: replicas finish `world` proofs every `ms`; sharded ranks finish one
         job_ms = ms if sharded else ms / world
         line = {
@@ -874,19 +935,25 @@ def main():
                        "value_is": ("ms per proof, one proof sharded over all ranks" if sharded
                                     else "ms per proof for the whole job = step time / ranks")},
             "aggregate_proofs_per_s": round((1 if sharded else world) * 1000.0 / ms, 4),
-            "ntt_hbm_gbs": round(lde_gbs, 1),
-            "stages_ms": {k: round(v, 3) for k, v in tm.as_dict().items() if k.endswith("_ms")},
-            "roofline": ntt_roofline(tm),
-            "ntt_valu": ntt_valu(tm),
-            "poseidon2": poseidon2_roofline(tm),
-            "openings": openings_roofline(tm),
-            "first_prove_after_setup_ms": round(first_ms, 3),
-            "cold_first_proof_ms": cold.get("first_prove_ms") if cold else None,
-            "cold_first_proof": cold,
             "proof_bytes": len(proof),
-            "proof_check": "host verifier accepted the proof; the last timed proof (and the last "
-                           "sustained one) are byte-identical to it",
+            "proof_check": "the last timed proof is byte-identical to the first warm-up proof "
+                           "(no host verification: --full runs it)",
         }
+        if tm is not None:  # --full: the proof timed with events, verified on the host
+            lde_gbs = tm.lde_bytes / (tm.lde_ms * 1e-3) / 1e9 if tm.lde_ms > 0 else 0.0
+            line.update({
+                "ntt_hbm_gbs": round(lde_gbs, 1),
+                "stages_ms": {k: round(v, 3) for k, v in tm.as_dict().items() if k.endswith("_ms")},
+                "roofline": ntt_roofline(tm),
+                "ntt_valu": ntt_valu(tm),
+                "poseidon2": poseidon2_roofline(tm),
+                "openings": openings_roofline(tm),
+                "first_prove_after_setup_ms": round(first_ms, 3),
+                "cold_first_proof_ms": cold.get("first_prove_ms") if cold else None,
+                "cold_first_proof": cold,
+                "proof_check": "host verifier accepted the proof; the last timed proof (and the "
+                               "last sustained one) are byte-identical to it",
+            })
         if "sustained" in extra:
             line["sustained"] = extra["sustained"]
         if world > 1 and not sharded and "sharded_proof" in extra:

@@ -5,7 +5,8 @@
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 tag=$1; shift
-O=gpurun_out/$tag
+OUT=${OUT:-bench_out}  # where the logs and result lines go
+O=$OUT/$tag
 S=$TMPDIR/$tag
 rm -rf $S $O && mkdir -p $S $O
 step() { echo "step $1 ($(date +%T))" >> $O/status; }
@@ -29,7 +30,7 @@ if [ -z "$SKIP_TESTS" ]; then
       -k "coset_lde or chunked or record_from_cycles or fibo_x4 or commit_root or repeat or batch" > $O/pytest.log 2>&1 || exit 1
   fi
 fi
-step bench && timeout -k 10 600 python bench.py --no-cpu-baseline $BENCH_ARGS > $O/bench.json 2> $O/bench.err && \
+step bench && timeout -k 10 600 python bench.py --full --no-cpu-baseline $BENCH_ARGS > $O/bench.json 2> $O/bench.err && \
 step done
 rc=$?
 echo "exit $rc"; cat $O/status; tail -2 $O/pytest.log

@@ -51,3 +51,23 @@ def test_overlapped_collective_is_charged_only_beyond_the_gpu_work_beside_it():
     assert m["overlapped_ms"] == pytest.approx(0.4 + full[2], abs=1e-3)
     # no overlap log (an untimed run): everything is charged
     assert bench.collective_model(log, 2)["modeled_ms"] == pytest.approx(sum(full), abs=1e-3)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
+    """--dump-outputs: one <name>.npy per array, float32 / float64 only, values unchanged, and a
+    dump past the 64 MB limit is refused before anything is written."""
+    import numpy as np
+    proof = bytes(range(256)) * 3
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), {"proof": np.frombuffer(proof, dtype=np.uint8).astype(np.float32),
+                                  "root": np.arange(8, dtype=np.float64) + 2.0**31})
+    got = np.load(out / "proof.npy")
+    assert got.dtype == np.float32 and bytes(got.astype(np.uint8)) == proof
+    assert np.load(out / "root.npy").tolist() == [2.0**31 + k for k in range(8)]
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    big = np.broadcast_to(np.float32(0), (bench.DUMP_LIMIT_BYTES // 4 + 1,))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": big})
+    assert not (tmp_path / "big").exists()
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(out), {"bytes": np.zeros(4, dtype=np.uint8)})
