@@ -10,6 +10,7 @@
 //! | `observe_into` (prover.rs:595-601)              | native Rust (same as StarkProvingKey)       |
 //! | `open` (prover.rs:242-553)                      | `bfz_open` + `bfz_proof_to_bincode`          |
 //! | `prove` (prover.rs:560-582)                     | `bfz_record_from_events` + record commit + open |
+//! | `debug_constraints` (prover.rs:139-149)         | `bfz_record_debug_constraints` (device traces) |
 //!
 //! `prove` overrides the default: instead of `generate_dependencies` + `generate_traces` on the
 //! host and a 1 GB trace upload, the record's event vectors (~50 B per cycle) go to the device,
@@ -563,9 +564,90 @@ impl MachineProver<SC, A> for HipProver {
         drop(rec);
         Ok(MachineProof { shard_proof })
     }
+
+    fn debug_constraints(
+        &self,
+        pk: &StarkProvingKey<SC>,
+        record: ExecutionRecord,
+        challenger: &mut Challenger<SC>,
+    ) where
+        A: for<'a> Air<DebugConstraintBuilder<'a, KoalaBear, <SC as StarkGenericConfig>::Challenge>>,
+    {
+        // prover.rs:139-149: the trait hands the host key over; the device key is the cached one
+        let dev = self.pk_to_device(pk);
+        self.debug_constraints_device(&dev, &record, challenger);
+    }
+}
+
+/// LookupKind argument index (crates/stark/src/lookup/lookup.rs:17-42) -> name.
+const KINDS: [&str; 8] = ["", "Memory", "Program", "Alu", "Jump", "MemInstr", "IO", "Byte"];
+
+/// What constraint `index` of a chip is, in Chip::eval's emission order (chip.rs:222-228): AIR
+/// constraints, one LogUp constraint per batch, then first-row, transition, last-row.
+fn constraint_name(c: &sys::bfz_chip_check) -> String {
+    let k_air = c.num_constraints - c.num_batches - 3;
+    let i = c.first_constraint;
+    if i < k_air {
+        format!("AIR constraint {i}")
+    } else if i < k_air + c.num_batches {
+        format!("LogUp batch {}", i - k_air)
+    } else {
+        ["LogUp first-row", "LogUp transition", "LogUp last-row"][(i - k_air - c.num_batches) as usize]
+            .to_string()
+    }
+}
+
+/// The report as text: chip, row and constraint of each chip's first failure and, for an
+/// unbalanced sum, the send-minus-receive count per lookup kind and chip (what the reference
+/// prints per key, lookup/debug.rs:136-196, summed per kind).
+pub fn report_text(r: &sys::bfz_debug_report) -> String {
+    let chips = &r.chips[..r.n_chips as usize];
+    let mut s = String::from(if r.ok != 0 { "constraints verified" } else { "constraints FAILED" });
+    for c in chips.iter().filter(|c| c.failing_rows != 0) {
+        s += &format!(
+            "\n  {} failing row(s) in chip {}: first at row {}, constraint {} of {} ({})",
+            c.failing_rows, CHIPS[c.chip as usize], c.first_row, c.first_constraint,
+            c.num_constraints, constraint_name(c));
+    }
+    if r.cumulative_sum.iter().any(|&w| w != 0) {
+        s += "\n  cumulative sum is not zero: the lookups do not balance";
+        if r.balance_valid != 0 {
+            for k in 1..sys::BFZ_NUM_KINDS {
+                let per_chip: Vec<String> = chips
+                    .iter()
+                    .filter(|c| r.kind_count[k][c.chip as usize] != 0)
+                    .map(|c| format!("{} {}", CHIPS[c.chip as usize], r.kind_net[k][c.chip as usize]))
+                    .collect();
+                let net: i64 = chips.iter().map(|c| r.kind_net[k][c.chip as usize] as i64).sum();
+                s += &format!("\n  {:<9} send - receive = {:<6} ({})", KINDS[k], net, per_chip.join(", "));
+            }
+        }
+    }
+    s
 }
 
 impl HipProver {
+    /// `MachineProver::debug_constraints` (prover.rs:139-149) on the device: the record goes to
+    /// HBM through the compact hand-over, every chip trace is generated there (the traces the GPU
+    /// proves from, not a host regeneration) and checked by bfz_record_debug_constraints
+    /// (StarkMachine::debug_constraints, machine.rs:288-387).  Panics with the report text where
+    /// the reference exits or panics (debug.rs:98-103, machine.rs:348).
+    pub fn debug_constraints_device(
+        &self,
+        pk: &HipProvingKey,
+        record: &ExecutionRecord,
+        challenger: &mut Challenger<SC>,
+    ) -> sys::bfz_debug_report {
+        let rec = HipRecord(CycleArrays::hand_over(pk.dev, record));
+        let mut ch = to_c(challenger);
+        let mut out = sys::bfz_debug_report::default();
+        sys::check(unsafe { sys::bfz_record_debug_constraints(pk.dev, rec.0, &mut ch, 0, &mut out) });
+        from_c(&ch, challenger); // two sample_ext_element (machine.rs:300-303)
+        drop(rec);
+        assert!(out.ok != 0, "{}", report_text(&out));
+        out
+    }
+
     /// Pipelined proofs of one program over many inputs (bfz_prove_batch): execution and event
     /// upload of job k+1 run under the GPU proof of job k.  Returns the reference's ShardProof
     /// per input.

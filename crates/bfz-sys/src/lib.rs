@@ -3,7 +3,7 @@
 //! i.e. the in-memory layout of `[KoalaBear]` (p3 `MontyField31`).
 #![allow(non_camel_case_types)]
 use core::ffi::c_void;
-use std::os::raw::{c_char, c_int};
+use std::os::raw::{c_char, c_int, c_uint};
 
 #[repr(C)]
 pub struct bfz_pk {
@@ -193,6 +193,40 @@ pub struct bfz_events {
     pub n_memory: usize,
 }
 
+pub const BFZ_NUM_CHIPS: usize = 8;
+/// LookupKind argument index 1..7 (lookup/lookup.rs:17-42); index 0 unused.
+pub const BFZ_NUM_KINDS: usize = 8;
+/// The row check of one chip (debug.rs:24-105): first failing row and constraint index.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct bfz_chip_check {
+    pub chip: i32,
+    pub num_constraints: i32,
+    pub height: u64,
+    pub failing_rows: u64,
+    pub first_row: i64,
+    pub first_constraint: i32,
+    pub num_batches: i32,
+    pub cumulative_sum: [u32; 4],
+}
+/// `StarkMachine::debug_constraints` (machine.rs:288-387) as plain data; `ok == 0` stands where
+/// the reference exits or panics.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct bfz_debug_report {
+    pub ok: i32,
+    pub n_chips: i32,
+    pub balance_valid: i32,
+    pub _pad: i32,
+    pub alpha: [u32; 4],
+    pub beta: [u32; 4],
+    pub cumulative_sum: [u32; 4],
+    pub chips: [bfz_chip_check; BFZ_NUM_CHIPS],
+    pub kind_sum: [[[u32; 4]; BFZ_NUM_CHIPS]; BFZ_NUM_KINDS],
+    pub kind_net: [[i32; BFZ_NUM_CHIPS]; BFZ_NUM_KINDS],
+    pub kind_count: [[u32; BFZ_NUM_CHIPS]; BFZ_NUM_KINDS],
+}
+
 pub type bfz_allgather_fn =
     Option<unsafe extern "C" fn(ctx: *mut c_void, send: *const c_void, bytes: usize, recv: *mut c_void) -> c_int>;
 pub type bfz_allreduce_u32_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, data: *mut u32, n: usize) -> c_int>;
@@ -217,6 +251,18 @@ extern "C" {
     pub fn bfz_perm_trace(chip: c_int, main: *const u32, prep: *const u32, height: usize,
                           alpha: *const u32, beta: *const u32, out: *mut *mut u32,
                           width: *mut usize, cumsum: *mut u32) -> c_int;
+    pub fn bfz_check_chip(chip: c_int, main: *const u32, prep: *const u32, perm: *const u32,
+                          height: usize, alpha: *const u32, beta: *const u32, cumsum: *const u32,
+                          on_device: c_int, out: *mut bfz_chip_check,
+                          first_fail_per_row: *mut i32) -> c_int;
+    pub fn bfz_record_debug_constraints(pk: *const bfz_pk, rec: *const bfz_record,
+                                        ch: *mut bfz_challenger, flags: c_uint,
+                                        out: *mut bfz_debug_report) -> c_int;
+    pub fn bfz_debug_constraints_traces(pk: *const bfz_pk, chips: *const c_int,
+                                        traces: *const *const u32, heights: *const usize,
+                                        widths: *const usize, nchips: usize,
+                                        ch: *mut bfz_challenger, flags: c_uint,
+                                        out: *mut bfz_debug_report) -> c_int;
     pub fn bfz_trace_device(elf: *const c_char, stdin_data: *const u8, nin: usize, chip: c_int,
                             out: *mut *mut u32, height: *mut usize, width: *mut usize) -> c_int;
 

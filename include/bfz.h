@@ -405,6 +405,77 @@ int bfz_commit_fri_sharded(const uint32_t* d_cols, int log_n, size_t w_local, in
                            bfz_allgather_fn allgather, void* ctx, uint32_t* out, size_t cap,
                            size_t* nwords);
 
+/* ---- Constraint checker: the reference's `--features debug` mode, on the device ----
+ * Replaces debug_constraints (crates/stark/src/debug.rs:24-105), StarkMachine::debug_constraints
+ * (crates/stark/src/machine.rs:288-387) and the interaction balance of
+ * debug_interactions_with_all_chips (crates/stark/src/lookup/debug.rs:59-196).
+ *
+ * Every row i of a chip's trace is checked against Chip::eval (chip.rs:222-228) with row
+ * (i + 1) mod height as the next row, is_first = [i == 0], is_last = [i == height - 1] and
+ * is_transition = 1 - is_last (debug.rs:43-94; a 1-row trace is its own next row).  A constraint
+ * is named by its 0-based position in the emission order of Chip::eval: the chip's AIR
+ * constraints, then one LogUp constraint per batch of two interactions, then the first-row,
+ * transition and last-row constraints of the running sum (permutation.rs:157-272).  AddSub has
+ * num_constraints = 14: 0-7 AIR, 8-10 batches, 11 first-row, 12 transition, 13 last-row.
+ *
+ * The reference stops the process at the first failing row (debug.rs:98-103) or panics on an
+ * unbalanced sum (machine.rs:337-349).  A library must not: these calls return 0 whenever the
+ * check RAN, whether or not the constraints hold, and report the outcome in `ok` /
+ * `failing_rows`; a negative status is a real error (bad shapes, a device error). */
+#define BFZ_NUM_CHIPS 8
+#define BFZ_NUM_KINDS 8 /* LookupKind argument index 1..7 (lookup/lookup.rs:17-42); 0 unused */
+typedef struct {
+  int32_t chip;             /* chip index, BfAir::chips() order */
+  int32_t num_constraints;  /* K: constraints Chip::eval emits for this chip */
+  uint64_t height;
+  uint64_t failing_rows;    /* rows with at least one non-zero constraint */
+  int64_t first_row;        /* the smallest failing row, -1 if none */
+  int32_t first_constraint; /* the first failing index at first_row, -1 if none */
+  int32_t num_batches;      /* LogUp batch constraints: indices [K - 3 - num_batches, K - 3) */
+  uint32_t cumulative_sum[4];
+} bfz_chip_check;
+typedef struct {
+  int32_t ok;            /* 1: every row of every chip holds and the total cumulative sum is 0 */
+  int32_t n_chips;       /* included chips; chips[0..n_chips) in machine order */
+  int32_t balance_valid; /* 1: the kind_* tables below were computed */
+  int32_t _pad;
+  uint32_t alpha[4], beta[4]; /* the LogUp challenges sampled from the challenger */
+  uint32_t cumulative_sum[4]; /* sum of the chips' cumulative sums (machine.rs:337) */
+  bfz_chip_check chips[BFZ_NUM_CHIPS];
+  /* Per LookupKind and chip index, over the rows' interactions with a non-zero multiplicity
+   * (lookup/debug.rs:79-116): kind_sum = sum of +-mult / (alpha + kind + sum_v beta^(v+1) val_v)
+   * (a chip's sum over kinds is its cumulative sum; a balanced kind sums to 0 over the chips),
+   * kind_net = sum of the signed multiplicities, sends positive, in the reference's field_to_int
+   * form (lookup/debug.rs:46-54: an integer in (-p/2, p/2]), kind_count = their number. */
+  uint32_t kind_sum[BFZ_NUM_KINDS][BFZ_NUM_CHIPS][4];
+  int32_t kind_net[BFZ_NUM_KINDS][BFZ_NUM_CHIPS];
+  uint32_t kind_count[BFZ_NUM_KINDS][BFZ_NUM_CHIPS];
+} bfz_debug_report;
+
+/* debug_constraints (debug.rs:24-105) of ONE chip, a diagnostic like bfz_perm_trace: main, prep
+ * (Program / Byte, else NULL) and perm are row-major Montgomery matrices of `height` rows, perm
+ * the flattened permutation trace exactly as bfz_perm_trace returns it; alpha, beta, cumsum as
+ * there.  on_device = 0 runs the checker's host path (the same templates, single-threaded, no
+ * device needed); 1 uploads the traces and runs the check kernel.  first_fail_per_row (optional,
+ * `height` entries) receives each row's first failing index, or -1. */
+int bfz_check_chip(int chip, const uint32_t* main, const uint32_t* prep, const uint32_t* perm,
+                   size_t height, const uint32_t alpha[4], const uint32_t beta[4],
+                   const uint32_t cumsum[4], int on_device, bfz_chip_check* out,
+                   int32_t* first_fail_per_row);
+/* StarkMachine::debug_constraints (machine.rs:288-387) on a device record: every chip trace is
+ * generated on the device as bfz_record_prove does, alpha then beta are sampled from ch (two
+ * sample_ext_element, machine.rs:300-303; ch is advanced, as in bfz_open), the permutation traces
+ * are generated (machine.rs:319-335), their cumulative sums added (:337) and every included chip
+ * checked (:369-384).  No LDE, no commit, no Merkle tree.  The kind_* balance table is computed
+ * when the total sum is not zero (machine.rs:338-349) or when flags bit 0 is set. */
+int bfz_record_debug_constraints(const bfz_pk* pk, const bfz_record* rec, bfz_challenger* ch,
+                                 unsigned flags, bfz_debug_report* out);
+/* The same from host main traces: arguments and validation of bfz_prove_traces, preprocessed
+ * traces from the key (machine.rs:309-312). */
+int bfz_debug_constraints_traces(const bfz_pk* pk, const int* chips, const uint32_t* const* traces,
+                                 const size_t* heights, const size_t* widths, size_t nchips,
+                                 bfz_challenger* ch, unsigned flags, bfz_debug_report* out);
+
 /* FRI_QUERIES (kb31_poseidon2.rs:59-62): 1..4096, or 0 = environment FRI_QUERIES / 84. */
 int bfz_set_num_queries(int num_queries);
 

@@ -8,7 +8,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p
+from ctypes import (POINTER, byref, c_char_p, c_double, c_int, c_int32, c_int64, c_size_t, c_uint, c_uint8,
+                    c_uint32, c_uint64, c_void_p)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(HERE), "libbfz.so")
@@ -50,6 +51,26 @@ class Challenger(ctypes.Structure):
                 ("n_input", c_uint32), ("output_buffer", c_uint32 * 8), ("n_output", c_uint32)]
 
 
+NUM_CHIPS, NUM_KINDS = 8, 8  # BFZ_NUM_CHIPS, BFZ_NUM_KINDS
+
+
+class ChipCheck(ctypes.Structure):
+    """bfz_chip_check: the row check of one chip (first failing row and constraint index)."""
+    _fields_ = [("chip", c_int32), ("num_constraints", c_int32), ("height", c_uint64),
+                ("failing_rows", c_uint64), ("first_row", c_int64), ("first_constraint", c_int32),
+                ("num_batches", c_int32), ("cumulative_sum", c_uint32 * 4)]
+
+
+class DebugReportC(ctypes.Structure):
+    """bfz_debug_report: StarkMachine::debug_constraints' outcome as plain data."""
+    _fields_ = [("ok", c_int32), ("n_chips", c_int32), ("balance_valid", c_int32), ("_pad", c_int32),
+                ("alpha", c_uint32 * 4), ("beta", c_uint32 * 4), ("cumulative_sum", c_uint32 * 4),
+                ("chips", ChipCheck * NUM_CHIPS),
+                ("kind_sum", ((c_uint32 * 4) * NUM_CHIPS) * NUM_KINDS),
+                ("kind_net", (c_int32 * NUM_CHIPS) * NUM_KINDS),
+                ("kind_count", (c_uint32 * NUM_CHIPS) * NUM_KINDS)]
+
+
 class Events(ctypes.Structure):
     """bfz_events: the reference ExecutionRecord's event arrays (pointers to bfz_*_event arrays,
     see bfz/events.py for their numpy layouts)."""
@@ -85,6 +106,14 @@ SIGNATURES = [
     ("bfz_perm_trace", c_int, [c_int, POINTER(c_uint32), POINTER(c_uint32), c_size_t,
                                POINTER(c_uint32), POINTER(c_uint32), POINTER(POINTER(c_uint32)),
                                POINTER(c_size_t), POINTER(c_uint32)]),
+    ("bfz_check_chip", c_int, [c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
+                               c_size_t, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
+                               c_int, POINTER(ChipCheck), POINTER(c_int32)]),
+    ("bfz_record_debug_constraints", c_int, [c_void_p, c_void_p, POINTER(Challenger), c_uint,
+                                             POINTER(DebugReportC)]),
+    ("bfz_debug_constraints_traces", c_int, [c_void_p, POINTER(c_int), POINTER(POINTER(c_uint32)),
+                                             POINTER(c_size_t), POINTER(c_size_t), c_size_t,
+                                             POINTER(Challenger), c_uint, POINTER(DebugReportC)]),
     ("bfz_trace_device", c_int, [c_char_p, POINTER(c_uint8), c_size_t, c_int,
                                  POINTER(POINTER(c_uint32)), POINTER(c_size_t), POINTER(c_size_t)]),
     ("bfz_setup", c_int, [c_char_p, POINTER(c_void_p), POINTER(c_uint32)]),
@@ -210,4 +239,5 @@ def take_bytes(ptr, n: int) -> bytes:
 
 
 __all__ = ["lib", "check", "init", "u8buf", "take_bytes", "BfzError", "Timings", "Events", "LIB_PATH",
+           "ChipCheck", "DebugReportC",
            "SIGNATURES", "byref"]

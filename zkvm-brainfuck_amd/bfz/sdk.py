@@ -17,6 +17,12 @@ and of the core MachineProver boundary (crates/stark/src/prover.rs:27-150):
     proof = prover.open(pk, data, ch)            # MachineProver::open      prover.rs:242-553
     proof = prover.prove(pk, traces)             # MachineProver::prove     prover.rs:560-582
 
+and of the reference's debug mode (crates/stark/src/machine.rs:288-387, debug.rs:24-105):
+
+    report = client.debug_constraints(pk, stdin) # StarkMachine::debug_constraints on the device
+    report = prover.debug_constraints(pk, traces)
+    print(report)                                # chip, row and constraint of the first failure
+
 Errors raise (the reference returns Err / panics in the same places).  Proving runs on the GPU
 through libbfz; verification runs the host verifier compiled into the same library.
 """
@@ -424,6 +430,188 @@ class BfProver:
 
     def verify(self, proof: BfProofWithPublicValues, vk: BfVerifyingKey) -> None:
         ProverClient().verify(proof, vk)
+
+
+# LookupKind argument index (crates/stark/src/lookup/lookup.rs:17-42) -> name
+KINDS = (None, "Memory", "Program", "Alu", "Jump", "MemInstr", "IO", "Byte")
+
+
+def constraint_name(index: int, num_constraints: int, num_batches: int) -> str:
+    """What constraint `index` of a chip with K = num_constraints is, in Chip::eval's emission
+    order (crates/stark/src/chip.rs:222-228): AIR constraints, one LogUp constraint per batch,
+    then the running sum's first-row, transition and last-row constraints
+    (permutation.rs:157-272)."""
+    k_air = num_constraints - num_batches - 3
+    if index < 0 or index >= num_constraints:
+        return "none"
+    if index < k_air:
+        return f"AIR constraint {index}"
+    if index < k_air + num_batches:
+        return f"LogUp batch {index - k_air}"
+    return ("LogUp first-row", "LogUp transition", "LogUp last-row")[index - k_air - num_batches]
+
+
+@dataclass
+class ChipCheckResult:
+    """bfz_chip_check: the row check of one chip."""
+    chip: int
+    height: int
+    num_constraints: int
+    num_batches: int
+    failing_rows: int
+    first_row: int
+    first_constraint: int
+    cumulative_sum: List[int]
+    first_fail_per_row: Optional[object] = None  # numpy int32[height] when asked for
+
+    @property
+    def name(self) -> str:
+        return CHIPS[self.chip]
+
+    def __str__(self) -> str:
+        head = f"{self.name:<12} {self.height:>8} rows, K = {self.num_constraints:<3}"
+        if not self.failing_rows:
+            return head + " ok"
+        return (f"{head} FAILED: {self.failing_rows} failing row(s); first: chip {self.name}, "
+                f"row {self.first_row}, constraint {self.first_constraint} of "
+                f"{self.num_constraints} ("
+                f"{constraint_name(self.first_constraint, self.num_constraints, self.num_batches)})")
+
+
+def _chip_result(c, per_row=None) -> ChipCheckResult:
+    return ChipCheckResult(chip=c.chip, height=c.height, num_constraints=c.num_constraints,
+                           num_batches=c.num_batches, failing_rows=c.failing_rows,
+                           first_row=c.first_row, first_constraint=c.first_constraint,
+                           cumulative_sum=list(c.cumulative_sum), first_fail_per_row=per_row)
+
+
+@dataclass
+class DebugReport:
+    """bfz_debug_report: what StarkMachine::debug_constraints (machine.rs:288-387) found.  Where
+    the reference exits or panics (debug.rs:98-103, machine.rs:348), ok is False and str(report)
+    names the chip, row and constraint.  kind_sum / kind_net / kind_count are indexed
+    [kind][chip index] (KINDS, CHIPS) and valid when balance_valid."""
+    ok: bool
+    chips: List[ChipCheckResult]
+    alpha: List[int]
+    beta: List[int]
+    cumulative_sum: List[int]
+    balance_valid: bool
+    kind_sum: list = field(default_factory=list)
+    kind_net: list = field(default_factory=list)
+    kind_count: list = field(default_factory=list)
+
+    def failing(self) -> List[ChipCheckResult]:
+        return [c for c in self.chips if c.failing_rows]
+
+    def __str__(self) -> str:
+        lines = ["constraints " + ("verified" if self.ok else "FAILED")]
+        lines += ["  " + str(c) for c in self.chips]
+        balanced = not any(self.cumulative_sum)
+        lines.append("  cumulative sum " + ("zero" if balanced else "NOT zero: the lookups do not balance"))
+        if self.balance_valid and not balanced:
+            inc = [c.chip for c in self.chips]
+            lines.append("  send - receive per lookup kind (count of sends minus receives; "
+                         "* = the kind's LogUp sum over the chips is not zero)")
+            lines.append("  " + f"{'kind':<10}" + "".join(f"{CHIPS[c]:>13}" for c in inc) + f"{'total':>13}")
+            for k in range(1, len(KINDS)):
+                bad = any(sum(self.kind_sum[k][c][e] for c in inc) % _P for e in range(4))
+                row = "".join(f"{self.kind_net[k][c]:>13}" if self.kind_count[k][c] else f"{'.':>13}"
+                              for c in inc)
+                lines.append("  " + f"{KINDS[k]:<10}" + row +
+                             f"{sum(self.kind_net[k][c] for c in inc):>13}" + (" *" if bad else ""))
+        return "\n".join(lines)
+
+
+_P = 0x7F000001
+
+
+def _report(r) -> DebugReport:
+    return DebugReport(
+        ok=bool(r.ok), chips=[_chip_result(r.chips[i]) for i in range(r.n_chips)],
+        alpha=list(r.alpha), beta=list(r.beta), cumulative_sum=list(r.cumulative_sum),
+        balance_valid=bool(r.balance_valid),
+        kind_sum=[[list(r.kind_sum[k][c]) for c in range(_lib.NUM_CHIPS)] for k in range(_lib.NUM_KINDS)],
+        kind_net=[list(r.kind_net[k]) for k in range(_lib.NUM_KINDS)],
+        kind_count=[list(r.kind_count[k]) for k in range(_lib.NUM_KINDS)])
+
+
+def check_chip(chip: int, main, prep, perm, alpha, beta, cumsum, on_device: bool = False,
+               per_row: bool = False) -> ChipCheckResult:
+    """debug_constraints (crates/stark/src/debug.rs:24-105) of one chip (bfz_check_chip): main,
+    prep (None without a preprocessed trace) and perm are (height, width) uint32 arrays in
+    Montgomery form, perm flattened to base as bfz_perm_trace returns it; alpha, beta and cumsum
+    are 4 Montgomery words.  on_device=False runs the host path (no GPU needed)."""
+    import numpy as np
+    P32 = ctypes.POINTER(ctypes.c_uint32)
+    m = np.ascontiguousarray(main, dtype=np.uint32)
+    pm = np.ascontiguousarray(perm, dtype=np.uint32)
+    pr = None if prep is None else np.ascontiguousarray(prep, dtype=np.uint32)
+    if m.ndim != 2 or pm.ndim != 2 or pm.shape[0] != m.shape[0] or (pr is not None and pr.shape[0] != m.shape[0]):
+        raise BfzError("check_chip: main, prep and perm must have the same number of rows")
+    if m.shape[1] != _MAIN_W[chip] or pm.shape[1] != _PERM_W[chip] or (
+            pr is not None and pr.shape[1] != _PREP_W[chip]):
+        raise BfzError(f"check_chip: wrong trace width for {CHIPS[chip]}")
+    if on_device:
+        init()
+    out = _lib.ChipCheck()
+    rows = np.zeros(m.shape[0], dtype=np.int32) if per_row else None
+    check(lib().bfz_check_chip(
+        int(chip), m.ctypes.data_as(P32), pr.ctypes.data_as(P32) if pr is not None else None,
+        pm.ctypes.data_as(P32), m.shape[0], (ctypes.c_uint32 * 4)(*alpha),
+        (ctypes.c_uint32 * 4)(*beta), (ctypes.c_uint32 * 4)(*cumsum), int(bool(on_device)),
+        ctypes.byref(out),
+        rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if per_row else None))
+    return _chip_result(out, rows)
+
+
+# main / preprocessed / flattened permutation widths per chip (CHIPS order)
+_MAIN_W = (31, 1, 7, 45, 12, 2, 41, 5)
+_PREP_W = (0, 6, 0, 0, 0, 2, 0, 0)
+_PERM_W = (36, 8, 16, 8, 12, 8, 8, 8)
+
+DEBUG_BALANCE = 1  # flags bit 0: compute the balance table even when the total sum is zero
+
+
+def _debug_constraints_traces(self, pk: BfProvingKey, traces, ch: Optional[Challenger] = None,
+                              flags: int = 0) -> DebugReport:
+    """StarkMachine::debug_constraints (machine.rs:288-387) from host main traces
+    (bfz_debug_constraints_traces): ch (default: a fresh challenger, which is what
+    utils/prove.rs:60 passes) is advanced by the two challenge samples."""
+    init()
+    mats, chips, ptrs, hs, ws, k = _trace_args(traces)
+    if ch is None:
+        ch = Challenger()
+    out = _lib.DebugReportC()
+    check(lib().bfz_debug_constraints_traces(ctypes.c_void_p(pk.handle), chips, ptrs, hs, ws, k,
+                                             ctypes.byref(ch), int(flags), ctypes.byref(out)))
+    return _report(out)
+
+
+def _debug_constraints_record(self, pk: BfProvingKey, stdin, ch: Optional[Challenger] = None,
+                              flags: int = 0) -> DebugReport:
+    """StarkMachine::debug_constraints (machine.rs:288-387) of (pk's program, stdin) on the
+    device: bfz_record_new, then bfz_record_debug_constraints checks the traces the GPU proves
+    from.  ch defaults to a fresh challenger (utils/prove.rs:60)."""
+    init(self.device)
+    buf, n = u8buf(bytes(stdin))
+    rec = ctypes.c_void_p()
+    cyc = ctypes.c_uint64()
+    check(lib().bfz_record_new(ctypes.c_void_p(pk.handle), buf, n, ctypes.byref(rec),
+                               ctypes.byref(cyc)))
+    try:
+        if ch is None:
+            ch = Challenger()
+        out = _lib.DebugReportC()
+        check(lib().bfz_record_debug_constraints(ctypes.c_void_p(pk.handle), rec, ctypes.byref(ch),
+                                                 int(flags), ctypes.byref(out)))
+    finally:
+        lib().bfz_record_free(rec)
+    return _report(out)
+
+
+CoreProver.debug_constraints = _debug_constraints_traces
+ProverClient.debug_constraints = _debug_constraints_record
 
 
 def set_num_queries(q: int) -> None:

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/bfz.h"
+#include "debug_check.h"
 #include "fri.h"
 #include "logup.h"
 #include "merkle.h"
@@ -436,6 +437,118 @@ int bfz_perm_trace(int chip, const uint32_t* main, const uint32_t* prep, size_t 
       for (int c = 0; c < w; c++) o[r * w + c] = cm[(size_t)c * n + bfz::bitrev32((uint32_t)r, logh)];
     *out = o;
     *width = w;
+    return 0;
+  });
+}
+
+}  // extern "C"
+namespace {
+void to_c(const bfz::ChipCheck& c, bfz_chip_check* o) {
+  o->chip = c.chip;
+  o->num_constraints = c.num_constraints;
+  o->height = c.height;
+  o->failing_rows = c.failing_rows;
+  o->first_row = c.first_row;
+  o->first_constraint = c.first_constraint;
+  o->num_batches = c.num_batches;
+  std::memcpy(o->cumulative_sum, c.cumsum.c, 16);
+}
+void to_c(const bfz::DebugReport& r, bfz_debug_report* o) {
+  static_assert(sizeof(bfz_chip_check) == 56 && sizeof(bfz_debug_report) == 64 + 8 * 56 + 1536,
+                "bfz_debug_report has no compiler-inserted gaps");
+  static_assert(BFZ_NUM_CHIPS == bfz::NUM_CHIPS && BFZ_NUM_KINDS == bfz::NUM_KINDS, "bfz.h sizes");
+  std::memset(o, 0, sizeof *o);
+  o->ok = r.ok;
+  o->n_chips = (int32_t)r.chips.size();
+  o->balance_valid = r.balance_valid;
+  std::memcpy(o->alpha, r.alpha.c, 16);
+  std::memcpy(o->beta, r.beta.c, 16);
+  std::memcpy(o->cumulative_sum, r.cumsum.c, 16);
+  for (size_t k = 0; k < r.chips.size(); k++) to_c(r.chips[k], &o->chips[k]);
+  for (int kind = 0; kind < bfz::NUM_KINDS; kind++)
+    for (int c = 0; c < bfz::NUM_CHIPS; c++) {
+      std::memcpy(o->kind_sum[kind][c], r.kind_sum[kind][c].c, 16);
+      o->kind_net[kind][c] = r.kind_net[kind][c];
+      o->kind_count[kind][c] = r.kind_count[kind][c];
+    }
+}
+kb::EF ef_arg(const uint32_t w[4], const char* what) {
+  kb::EF e;
+  std::memcpy(e.c, w, 16);
+  for (int k = 0; k < 4; k++)
+    if (e.c[k] >= kb::P) throw std::runtime_error(std::string("non-canonical ") + what);
+  return e;
+}
+}  // namespace
+extern "C" {
+
+int bfz_check_chip(int chip, const uint32_t* main, const uint32_t* prep, const uint32_t* perm,
+                   size_t n, const uint32_t alpha[4], const uint32_t beta[4],
+                   const uint32_t cumsum[4], int on_device, bfz_chip_check* out,
+                   int32_t* first_fail_per_row) {
+  return guarded([&] {
+    if (chip < 0 || chip >= bfz::NUM_CHIPS) throw std::runtime_error("bad chip index");
+    if (!main || !perm || !alpha || !beta || !cumsum || !out) throw std::runtime_error("null argument");
+    if (n == 0 || (n & (n - 1)) || n > ((size_t)1 << 23)) throw std::runtime_error("height must be a power of two");
+    const int mw = bfz::CHIP_INFO[chip].main_w, pwid = bfz::CHIP_INFO[chip].prep_w;
+    const int w = 4 * bfz::perm_width(chip);
+    if (pwid && !prep) throw std::runtime_error("this chip has a preprocessed trace");
+    const kb::EF a = ef_arg(alpha, "challenge"), b = ef_arg(beta, "challenge"),
+                 cs = ef_arg(cumsum, "cumulative sum");
+    bfz::ChipCheck cc;
+    if (!on_device) {
+      // mmul needs words < p, and the check compares reduced words with 0
+      auto canonical = [&](const uint32_t* m, size_t words) {
+        for (size_t i = 0; i < words; i++)
+          if (m[i] >= kb::P) throw std::runtime_error("non-canonical field word");
+      };
+      canonical(main, n * mw);
+      if (pwid) canonical(prep, n * pwid);
+      canonical(perm, n * w);
+      bfz::check_chip_host(chip, main, prep, perm, n, a, b, cs, cc, first_fail_per_row);
+      to_c(cc, out);
+      return 0;
+    }
+    hipStream_t st = bfz::stream();
+    auto colmajor = [&](const uint32_t* rm, int cols) {
+      bfz::DBuf<uint32_t> r(n * cols), c(n * cols);
+      bfz::upload_bulk(r.p, rm, n * cols * 4, st);
+      if (bfz::count_noncanonical(r.p, n * cols, st)) throw std::runtime_error("non-canonical field word");
+      bfz::transpose_bitrev(r.p, n, cols, c.p, st);
+      return c;
+    };
+    bfz::DBuf<uint32_t> mc = colmajor(main, mw), pe = colmajor(perm, w);
+    bfz::DBuf<uint32_t> pc;
+    if (pwid) pc = colmajor(prep, pwid);
+    bfz::PermChallenges ch;
+    ch.alpha = a;
+    ch.beta_pows[0] = kb::ef_one();
+    for (int j = 1; j < 8; j++) ch.beta_pows[j] = kb::ef_mul(ch.beta_pows[j - 1], b);
+    bfz::DBuf<bfz::PermChallenges> chd(1);
+    bfz::DBuf<kb::EF> csd(1);
+    bfz::DBuf<unsigned long long> resd(2);
+    bfz::DBuf<int32_t> rowd;
+    if (first_fail_per_row) rowd.reset(n);
+    unsigned long long res[2] = {~0ull, 0};
+    HIP_CHECK(hipMemcpyAsync(chd.p, &ch, sizeof(ch), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(csd.p, &cs, sizeof(cs), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(resd.p, res, sizeof(res), hipMemcpyHostToDevice, st));
+    bfz::check_chip_device(chip, mc.p, pwid ? pc.p : nullptr, pe.p, n, chd.p, csd.p, resd.p,
+                           first_fail_per_row ? rowd.p : nullptr, st);
+    std::vector<int32_t> rows(first_fail_per_row ? n : 0);
+    HIP_CHECK(hipMemcpyAsync(res, resd.p, sizeof(res), hipMemcpyDeviceToHost, st));
+    if (first_fail_per_row)
+      HIP_CHECK(hipMemcpyAsync(rows.data(), rowd.p, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    bfz::fill_chip_header(chip, n, cc);
+    cc.cumsum = cs;
+    bfz::decode_check_result(res, cc);
+    if (first_fail_per_row) {
+      const int logh = bfz::log2i(n);
+      for (size_t r = 0; r < n; r++)  // storage position -> natural row
+        first_fail_per_row[r] = rows[bfz::bitrev32((uint32_t)r, logh)];
+    }
+    to_c(cc, out);
     return 0;
   });
 }
@@ -1075,6 +1188,38 @@ int bfz_record_prove(const bfz_pk* pk, const bfz_record* rec, uint8_t** proof, s
     const int r = emit(std::move(v), proof, len);
     bfz::host_mark("emitted");
     return r;
+  });
+}
+
+int bfz_record_debug_constraints(const bfz_pk* pk, const bfz_record* rec, bfz_challenger* ch,
+                                 unsigned flags, bfz_debug_report* out) {
+  return guarded([&] {
+    if (!pk || !rec || !ch || !out) throw std::runtime_error("null argument");
+    bfz::Challenger c = from_c(ch);
+    bfz::DeviceTraces dt;
+    bfz::generate_traces_device(rec->ev, dt, bfz::stream());
+    bfz::DebugReport r;
+    bfz::debug_constraints_device(*pk->pk, dt, c, (flags & 1) != 0, r);
+    to_c(r, out);
+    to_c(c, ch);  // debug_constraints samples from its &mut challenger (machine.rs:300-303)
+    return 0;
+  });
+}
+
+int bfz_debug_constraints_traces(const bfz_pk* pk, const int* chips, const uint32_t* const* traces,
+                                 const size_t* heights, const size_t* widths, size_t nchips,
+                                 bfz_challenger* ch, unsigned flags, bfz_debug_report* out) {
+  return guarded([&] {
+    if (!pk || !chips || !traces || !heights || !widths || !ch || !out)
+      throw std::runtime_error("null argument");
+    bfz::Challenger c = from_c(ch);
+    bfz::DeviceTraces dt;
+    bfz::upload_host_traces(chips, traces, heights, widths, nchips, dt, bfz::stream());
+    bfz::DebugReport r;
+    bfz::debug_constraints_device(*pk->pk, dt, c, (flags & 1) != 0, r);
+    to_c(r, out);
+    to_c(c, ch);
+    return 0;
   });
 }
 

@@ -1,0 +1,187 @@
+// Constraint checker: the reference's `--features debug` mode on the device.
+//   debug_constraints                      crates/stark/src/debug.rs:24-105
+//   StarkMachine::debug_constraints        crates/stark/src/machine.rs:288-387
+//   debug_interactions_with_all_chips      crates/stark/src/lookup/debug.rs:59-196
+// The AIRs and the LogUp constraints are the templates of air.h, evaluated on the TRACE domain
+// with a third accumulator (FirstFailAcc) instead of the quotient's alpha fold: row i is local,
+// row (i + 1) mod h is next, is_first = [i == 0], is_last = [i == h - 1], is_transition =
+// 1 - is_last (debug.rs:43-94).  The row functions are KB_HD: the host path of bfz_check_chip
+// runs the same code single-threaded, the kernels of debug_check.hip one row per thread.
+//
+// Constraint index: the 0-based position in Chip::eval's emission order (chip.rs:222-228): the
+// chip's AIR constraints, one LogUp constraint per batch, then first-row, transition, last-row
+// (permutation.rs:157-272) -- the order num_constraints(chip) counts.
+#pragma once
+#include <vector>
+
+#include "air.h"
+#include "logup.h"
+#include "prover.h"
+
+namespace bfz {
+
+constexpr int NUM_KINDS = 8;  // LookupKind 1..7 (lookup.rs:17-42); index 0 unused
+constexpr int DBG_MAIN_W[NUM_CHIPS] = {31, 1, 7, 45, 12, 2, 41, 5};
+constexpr int DBG_PREP_W[NUM_CHIPS] = {0, 6, 0, 0, 0, 2, 0, 0};
+constexpr int DBG_PERM_W[NUM_CHIPS] = {9, 2, 4, 2, 3, 2, 2, 2};  // EF columns
+
+// Counts the emissions and remembers the first one that is not zero.  Every value kb::madd /
+// msub / mmul / mneg return is reduced to [0, p) (one umin against the -p / +p candidate), and
+// the inputs are checked to be canonical words before they get here, so a constraint holds
+// exactly when its word is 0.
+struct FirstFailAcc {
+  int n = 0, first = -1;
+  KB_HD void emit(uint32_t c) {
+    if (c != 0 && first < 0) first = n;
+    n++;
+  }
+  KB_HD void emit_ext(const EF& c) {
+    if (!kb::ef_is_zero(c) && first < 0) first = n;
+    n++;
+  }
+};
+
+// Chip::eval on one row of the trace domain (debug.rs:43-97): the first failing constraint
+// index, or -1.  L / N: main local / next; PL / PN: preprocessed; pl / pn: permutation (EF).
+template <int CHIP>
+KB_HD int check_row(const uint32_t* L, const uint32_t* N, const uint32_t* PL, const uint32_t* PN,
+                    const EF* pl, const EF* pn, bool is_first, bool is_last, const EF& alpha,
+                    const EF* beta_pows, const EF& cumsum) {
+  const uint32_t first = is_first ? kb::ONE : 0, last = is_last ? kb::ONE : 0,
+                 trans = is_last ? 0 : kb::ONE;
+  FirstFailAcc acc;
+  Air<BaseOps, FirstFailAcc> air{L, N, PL, PN, first, last, trans, acc};
+  air.template eval_air<CHIP>();
+  air.template eval_perm<CHIP>(pl, pn, alpha, beta_pows, cumsum, kb::ef_base(first),
+                               kb::ef_base(last), kb::ef_base(trans));
+  return acc.first;
+}
+
+// One row's interactions for the balance table (lookup/debug.rs:79-116): per LookupKind the sum
+// of +-mult / (alpha + kind + sum_v beta^(v+1) val_v) over the chip's lookups whose multiplicity
+// is not zero, the sum of the signed multiplicities (a field element) and their number.  The
+// denominators of the row are inverted together (one EF inversion per row).
+struct KindSums {
+  EF sum[NUM_KINDS];
+  uint32_t net[NUM_KINDS];
+  uint32_t count[NUM_KINDS];
+  KB_HD void clear() {
+#pragma unroll
+    for (int k = 0; k < NUM_KINDS; k++) {
+      sum[k] = kb::ef_zero();
+      net[k] = 0;
+      count[k] = 0;
+    }
+  }
+};
+
+template <int CHIP, int J, int NL>
+KB_HD void balance_gather(const Air<BaseOps, FirstFailAcc>& air, const EF& alpha,
+                          const EF* beta_pows, EF (&den)[NL], uint32_t (&mult)[NL]) {
+  if constexpr (J < NL) {
+    EF r, m;
+    air.template rlc_mult<CHIP, J>(alpha, beta_pows, r, m);
+    mult[J] = m.c[0];  // the signed multiplicity is a base-field value
+    // a zero multiplicity contributes nothing; a zero denominator (probability ~ 2^-124 per
+    // interaction) has no inverse: both are skipped, with 1 in the batch inversion
+    if (mult[J] == 0 || kb::ef_is_zero(r)) {
+      mult[J] = 0;
+      r = kb::ef_one();
+    }
+    den[J] = r;
+    balance_gather<CHIP, J + 1, NL>(air, alpha, beta_pows, den, mult);
+  }
+}
+
+template <int CHIP, int J, int NL>
+KB_HD void balance_scatter(const EF (&inv)[NL], const uint32_t (&mult)[NL], KindSums& ks) {
+  if constexpr (J < NL) {
+    constexpr int kind = LookupsOf<CHIP>::v.l[J].kind;
+    if (mult[J] != 0) {
+      ks.sum[kind] = kb::ef_add(ks.sum[kind], kb::ef_mul_base(inv[J], mult[J]));
+      ks.net[kind] = kb::madd(ks.net[kind], mult[J]);
+      ks.count[kind] += 1;
+    }
+    balance_scatter<CHIP, J + 1, NL>(inv, mult, ks);
+  }
+}
+
+template <int CHIP>
+KB_HD void balance_row(const uint32_t* L, const uint32_t* PL, const EF& alpha, const EF* beta_pows,
+                       KindSums& ks) {
+  constexpr int NL = LookupsOf<CHIP>::v.n;
+  FirstFailAcc unused;
+  Air<BaseOps, FirstFailAcc> air{L, L, PL, PL, 0, 0, 0, unused};
+  EF den[NL], inv[NL];
+  uint32_t mult[NL];
+  balance_gather<CHIP, 0, NL>(air, alpha, beta_pows, den, mult);
+  // Montgomery's trick: inv[j] first holds d_0 .. d_(j-1), then 1 / d_j
+  EF run = kb::ef_one();
+#pragma unroll
+  for (int j = 0; j < NL; j++) {
+    inv[j] = run;
+    run = kb::ef_mul(run, den[j]);
+  }
+  run = kb::ef_inv(run);
+#pragma unroll
+  for (int j = NL - 1; j >= 0; j--) {
+    inv[j] = kb::ef_mul(inv[j], run);
+    run = kb::ef_mul(run, den[j]);
+  }
+  balance_scatter<CHIP, 0, NL>(inv, mult, ks);
+}
+
+// ------------------------------------------------------------------------ results
+struct ChipCheck {
+  int chip = -1;
+  size_t height = 0;
+  int num_constraints = 0;
+  int num_batches = 0;        // LogUp batch constraints: indices [K - 3 - batches, K - 3)
+  uint64_t failing_rows = 0;
+  int64_t first_row = -1;     // smallest failing row, -1 if none
+  int first_constraint = -1;  // first failing index at that row, -1 if none
+  EF cumsum{};
+};
+
+struct DebugReport {
+  bool ok = false;
+  std::vector<ChipCheck> chips;  // included chips in machine order
+  EF alpha{}, beta{}, cumsum{};
+  bool balance_valid = false;
+  // [kind][chip id]: LogUp sum, signed multiplicity sum (field_to_int, lookup/debug.rs:46-54) and
+  // number of non-zero interactions
+  EF kind_sum[NUM_KINDS][NUM_CHIPS] = {};
+  int32_t kind_net[NUM_KINDS][NUM_CHIPS] = {};
+  uint32_t kind_count[NUM_KINDS][NUM_CHIPS] = {};
+};
+
+// Host path: row-major natural-order traces (Montgomery); perm = the flattened permutation
+// trace (h x 4 perm_width).  per_row (optional, h entries): first failing index or -1.
+void check_chip_host(int chip, const uint32_t* main, const uint32_t* prep, const uint32_t* perm,
+                     size_t h, const EF& alpha, const EF& beta, const EF& cumsum, ChipCheck& out,
+                     int32_t* per_row);
+
+// Device path: column-major bit-reversed traces in HBM (gpu.h LAYOUT), the challenges and the
+// chip's cumulative sum in device memory.  res receives {min(row * K + idx) or ~0, failing rows};
+// per_row_dev (optional): first failing index or -1 per STORAGE position.
+void check_chip_device(int chip, const uint32_t* mainc, const uint32_t* prepc,
+                       const uint32_t* permc, size_t h, const PermChallenges* ch_dev,
+                       const EF* cumsum_dev, unsigned long long* res_dev, int32_t* per_row_dev,
+                       hipStream_t st);
+// chip, height, K and the number of LogUp batches of a result.
+void fill_chip_header(int chip, size_t h, ChipCheck& out);
+// Fills out.{failing_rows, first_row, first_constraint} from the two downloaded words.
+void decode_check_result(const unsigned long long res[2], ChipCheck& out);
+
+// out_dev: NUM_KINDS x 6 words (sum[4], net, count) of one chip, reduced over its rows.
+void lookup_balance_device(int chip, const uint32_t* mainc, const uint32_t* prepc, size_t h,
+                           const PermChallenges* ch_dev, uint32_t* out_dev, hipStream_t st);
+
+// StarkMachine::debug_constraints (machine.rs:288-387) on device-resident main traces: samples
+// alpha then beta from ch (advanced), generates the permutation traces, sums the cumulative
+// sums, checks every chip and, when the sum is not zero or force_balance, fills the balance
+// table.  No LDE, no commit.
+void debug_constraints_device(const ProvingKey& pk, const DeviceTraces& dt, Challenger& ch,
+                              bool force_balance, DebugReport& out);
+
+}  // namespace bfz
