@@ -16,28 +16,113 @@ namespace bfz {
 
 using namespace kb;
 
-// The columns hashed at one height: up to MAXSEG matrices ("segments"), segment s holding
-// columns [start[s], start[s+1]) at base[s] + (c - start[s]) * stride[s].
+// The columns hashed at one height: up to MAXSEG matrices ("segments") in commit order, each
+// with at least one column; column k of a segment is at base + k * stride.
 constexpr int MAXSEG = 16;
+struct ColSeg {
+  const uint32_t* base;
+  size_t stride;
+  int n;  // columns
+};
 struct ColList {
-  const uint32_t* base[MAXSEG];
-  size_t stride[MAXSEG];
-  int start[MAXSEG + 1];
+  ColSeg seg[MAXSEG];
   int nseg;
-  int n;
-  __device__ __forceinline__ const uint32_t* col(int c) const {
-    int s = 0;
-    while (s + 1 < nseg && c >= start[s + 1]) s++;
-    return base[s] + (size_t)(c - start[s]) * stride[s];
+  int n;  // columns of all segments
+};
+
+// A walk over a ColList's columns in order.  The list sits in the kernarg segment and the walk
+// is wave-uniform, so its state lives in SGPRs: a step to the next column is a scalar add, and
+// only a segment's end loads anything (the next segment's base / stride / count).
+struct ColWalk {
+  const uint32_t* p;  // the next column
+  size_t stride;
+  int left;           // columns left in segment s, p's included
+  int s;
+  __device__ __forceinline__ void enter(const ColList& cl, int seg) {
+    s = seg;
+    p = nullptr;
+    stride = 0;
+    left = 0;
+    if (seg < cl.nseg) {
+      p = cl.seg[seg].base;
+      stride = cl.seg[seg].stride;
+      left = cl.seg[seg].n;
+    }
+  }
+  // Past the list's last column the walk stays on it: a caller may always load through the
+  // returned pointer (a short chunk's surplus loads re-read that column and are not used).
+  __device__ __forceinline__ const uint32_t* next(const ColList& cl) {
+    const uint32_t* r = p;
+    if (left > 1) {
+      left--;
+      p += stride;
+    } else if (s + 1 < cl.nseg) {
+      enter(cl, s + 1);
+    }
+    return r;
+  }
+  // Lane mode: the next m <= 8 columns, lane k < m getting column k's pointer (one multiply-add
+  // per segment the chunk touches, no per-lane search).
+  __device__ __forceinline__ const uint32_t* next_lanes(const ColList& cl, int m, int lane) {
+    const uint32_t* r = nullptr;
+    for (int k0 = 0; k0 < m && left > 0;) {
+      const int take = m - k0 < left ? m - k0 : left;
+      const int k = lane - k0;
+      if (k >= 0 && k < take) r = p + (size_t)k * stride;
+      k0 += take;
+      if (left > take) {
+        left -= take;
+        p += (size_t)take * stride;
+      } else {
+        enter(cl, s + 1);
+      }
+    }
+    return r;
   }
 };
 
-__device__ __forceinline__ void sponge_cols(uint32_t st[16], const ColList& cl, size_t row) {
-  for (int c0 = 0; c0 < cl.n; c0 += 8) {
+// Word `off4 / 4` of a column.  A 32-bit byte offset keeps the address a scalar base plus one
+// VGPR (make_cols refuses columns longer than 4 GiB).
+__device__ __forceinline__ uint32_t ld_col(const uint32_t* col, uint32_t off4) {
+  return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(col) + off4);
+}
+
+// The next 8 columns' words of one row (a list with at least one column; see ColWalk::next for
+// the list's end).  Straight-line: eight loads in flight together.
+__device__ __forceinline__ void load_chunk(uint32_t nx[8], ColWalk& w, const ColList& cl,
+                                           uint32_t off4) {
 #pragma unroll
-    for (int k = 0; k < 8; k++)
-      if (c0 + k < cl.n) st[k] = cl.col(c0 + k)[row];
-    poseidon2_permute(st);
+  for (int k = 0; k < 8; k++) nx[k] = ld_col(w.next(cl), off4);
+}
+
+// Overwrite-mode absorb: st[0..m) = nx[0..m).
+__device__ __forceinline__ void take_chunk(uint32_t st[16], const uint32_t nx[8], int m) {
+  if (m == 8) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) st[k] = nx[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 7; k++) st[k] = k < m ? nx[k] : st[k];
+  }
+}
+
+// PaddingFreeSponge of one row over the list's columns, st zero on entry; only st[0..8) (the
+// digest) is finished on return.  The first permutation starts from a zero capacity, one that
+// a full chunk follows leaves st[0..8) unfinished (overwritten unread), the last one st[8..16).
+// (Issuing a chunk's loads before the previous chunk's permutation, 8 more VGPRs, was no
+// faster in either kernel, and holding them to the old 6 / 5 waves per SIMD was slower:
+// profiles/r07/ab_merkle_ends.txt.)
+__device__ __forceinline__ void sponge_cols(uint32_t st[16], const ColList& cl, uint32_t off4) {
+  ColWalk w;
+  w.enter(cl, 0);
+  bool first = true;
+  for (int rest = cl.n; rest > 0; first = false) {
+    const int m = rest < 8 ? rest : 8;
+    uint32_t nx[8];
+    load_chunk(nx, w, cl, off4);
+    take_chunk(st, nx, m);
+    rest -= m;
+    poseidon2_permute_ends(st, first, rest < 8, rest > 0);
   }
 }
 
@@ -50,22 +135,26 @@ __global__ __launch_bounds__(256) void k_hash_leaves(ColList cl, size_t r0, size
   uint32_t st[16];
 #pragma unroll
   for (int i = 0; i < 16; i++) st[i] = 0;
-  sponge_cols(st, cl, r);
+  sponge_cols(st, cl, (uint32_t)r * 4u);
   uint4* o = reinterpret_cast<uint4*>(out + 8 * r);
   o[0] = make_uint4(st[0], st[1], st[2], st[3]);
   o[1] = make_uint4(st[4], st[5], st[6], st[7]);
 }
 
-// Merkle node j from its two children already in st[0..16]:
-//   compress(children), then with injected columns [c0, c1): compress(node, sponge(row j)).
+// Merkle node from its two children already in st[0..16]:
+//   compress(children), then with injected columns: compress(node, sponge(the node's row)).
 // The steps share ONE permutation call site, so the kernel holds a single inlined copy of
-// the (~37 KB) permutation instead of three.
-__device__ __forceinline__ void merkle_node(uint32_t st[16], const ColList& cl, int c0, int c1,
-                                            size_t j) {
-  const int nchunks = (c1 - c0 + 7) >> 3;
+// the (~27 KB) permutation core instead of three; each step picks its ends (both compressions
+// and the sponge's last permutation are read in [0..8) only).
+__device__ __forceinline__ void merkle_node(uint32_t st[16], const ColList& cl, uint32_t off4) {
+  const int nchunks = (cl.n + 7) >> 3;
   const int nsteps = nchunks ? nchunks + 2 : 1;
+  ColWalk w;
+  w.enter(cl, 0);
   uint32_t d[8];
+  int rest = cl.n;
   for (int step = 0; step < nsteps; step++) {
+    bool lo = true, hi = false;
     if (step == 1) {
 #pragma unroll
       for (int i = 0; i < 8; i++) d[i] = st[i];
@@ -73,10 +162,15 @@ __device__ __forceinline__ void merkle_node(uint32_t st[16], const ColList& cl, 
       for (int i = 0; i < 16; i++) st[i] = 0;
     }
     if (step >= 1 && step <= nchunks) {
-      const int cb = c0 + 8 * (step - 1);
-#pragma unroll
-      for (int k = 0; k < 8; k++)
-        if (cb + k < c1) st[k] = cl.col(cb + k)[j];
+      const int m = rest < 8 ? rest : 8;
+      uint32_t nx[8];
+      load_chunk(nx, w, cl, off4);
+      take_chunk(st, nx, m);
+      rest -= m;
+      if (rest > 0) {  // another chunk follows
+        lo = rest < 8;
+        hi = true;
+      }
     }
     if (nchunks && step == nchunks + 1) {
 #pragma unroll
@@ -85,7 +179,7 @@ __device__ __forceinline__ void merkle_node(uint32_t st[16], const ColList& cl, 
         st[i] = d[i];
       }
     }
-    poseidon2_permute(st);
+    poseidon2_permute_ends(st, step == 1, lo, hi);
   }
 }
 
@@ -113,22 +207,25 @@ __global__ __launch_bounds__(256) void k_compress(const uint32_t* __restrict__ p
   const size_t j = j0 + i;
   uint32_t st[16];
   load16(st, prev + 16 * j);
-  merkle_node(st, inj, 0, inj.n, j);
+  merkle_node(st, inj, (uint32_t)j * 4u);
   store8(out + 8 * j, st);
 }
 
 // Merkle node j in lane mode (see poseidon2_permute_lane): lane l of the node's 16-lane row
-// holds word l of the state; the digest ends up in lanes 0..7.
-__device__ __forceinline__ uint32_t merkle_node_lane(uint32_t v, const ColList& cl, int c0, int c1,
+// holds word l of the state; the digest ends up in lanes 0..7.  The injected columns are the
+// nc columns from segment s0 on.
+__device__ __forceinline__ uint32_t merkle_node_lane(uint32_t v, const ColList& cl, int s0, int nc,
                                                      size_t j, int lane, const LaneConsts& kc) {
+  ColWalk w;
+  w.enter(cl, s0);
   v = poseidon2_permute_lane(v, lane, kc);
-  const int nchunks = (c1 - c0 + 7) >> 3;
-  if (nchunks) {
+  if (nc > 0) {
     const uint32_t d = v;
     uint32_t h = 0;
-    for (int k = 0; k < nchunks; k++) {  // PaddingFreeSponge, overwrite mode
-      const int col = c0 + 8 * k + lane;
-      if (lane < 8 && col < c1) h = cl.col(col)[j];
+    for (int rest = nc; rest > 0; rest -= 8) {  // PaddingFreeSponge, overwrite mode
+      const int m = rest < 8 ? rest : 8;
+      const uint32_t* col = w.next_lanes(cl, m, lane);
+      if (lane < m && col) h = col[j];
       h = poseidon2_permute_lane(h, lane, kc);
     }
     const uint32_t hs = dpp<DPP_ROR8>(h);  // lanes 8..15 <- h[0..7]
@@ -155,7 +252,7 @@ constexpr size_t LANE_LAYER_MAX = (size_t)1 << 14;
 constexpr int MAXTOP = TOP_LAYERS;
 struct TopLayers {
   uint32_t* out[MAXTOP];
-  int c0[MAXTOP], c1[MAXTOP];
+  int s0[MAXTOP], nc[MAXTOP];  // a layer injects nc columns, from segment s0 of the list on
   int n;  // layers in this launch
 };
 
@@ -176,7 +273,7 @@ __global__ __launch_bounds__(1024) void k_compress_top(const uint32_t* __restric
     // from HBM, the rest from LDS (one pointer for both would compile to flat loads)
     for (size_t j = threadIdx.x >> 4; j < m; j += blockDim.x >> 4) {
       const uint32_t x = l == 0 ? ld_global(prev, 16 * (g + j) + lane) : src[16 * j + lane];
-      const uint32_t v = merkle_node_lane(x, inj, tl.c0[l], tl.c1[l], g + j, lane, kc);
+      const uint32_t v = merkle_node_lane(x, inj, tl.s0[l], tl.nc[l], g + j, lane, kc);
       if (lane < 8) {
         tl.out[l][8 * (g + j) + lane] = v;
         dst[8 * j + lane] = v;
@@ -260,15 +357,29 @@ static ColList make_cols(const std::vector<const MatRef*>& ms) {
   cl.n = 0;
   cl.nseg = 0;
   for (const MatRef* m : ms) {
+    if (m->width <= 0) continue;  // a segment has at least one column (ColWalk)
     if (cl.nseg >= MAXSEG) throw std::runtime_error("merkle: too many matrices at one height");
-    cl.base[cl.nseg] = m->base;
-    cl.stride[cl.nseg] = m->stride ? m->stride : m->height;
-    cl.start[cl.nseg] = cl.n;
+    // ld_col addresses a column's words by a 32-bit byte offset
+    if (m->height > ((size_t)1 << 30)) throw std::runtime_error("merkle: matrix taller than 2^30");
+    cl.seg[cl.nseg].base = m->base;
+    cl.seg[cl.nseg].stride = m->stride ? m->stride : m->height;
+    cl.seg[cl.nseg].n = m->width;
     cl.nseg++;
     cl.n += m->width;
   }
-  cl.start[cl.nseg] = cl.n;
   return cl;
+}
+
+// The injected columns of one layer of a k_compress_top launch: `all` holds the matrices of
+// the launch's earlier layers; the layer's own (height nlen) are appended from sorted[next..].
+static void top_layer_cols(TopLayers& tl, int l, std::vector<const MatRef*>& all,
+                           const std::vector<const MatRef*>& sorted, size_t& next, size_t nlen) {
+  tl.s0[l] = make_cols(all).nseg;
+  tl.nc[l] = 0;
+  while (next < sorted.size() && sorted[next]->height == nlen) {
+    tl.nc[l] += sorted[next]->width;
+    all.push_back(sorted[next++]);
+  }
 }
 
 // One layer's nodes [j0, j0 + count) from layers[L-1] (lane mode for small launches).
@@ -315,11 +426,7 @@ static void build_layers(MerkleTree& t, int L0, size_t len, const std::vector<co
     std::vector<const MatRef*> all;
     size_t nlen = first;
     for (int l = 0; l < tl.n; l++, nlen >>= 1) {
-      tl.c0[l] = 0;
-      for (const MatRef* m : all) tl.c0[l] += m->width;
-      while (next < sorted.size() && sorted[next]->height == nlen) all.push_back(sorted[next++]);
-      tl.c1[l] = 0;
-      for (const MatRef* m : all) tl.c1[l] += m->width;
+      top_layer_cols(tl, l, all, sorted, next, nlen);
       t.layers[L + l].reset(8 * nlen);
       tl.out[l] = t.layers[L + l].p;
     }
@@ -381,11 +488,7 @@ static void build_sharded(MerkleTree& t, size_t h0, const std::vector<const MatR
     std::vector<const MatRef*> all;
     size_t nlen = len >> 1;
     for (int l = 0; l < tl.n; l++, nlen >>= 1) {
-      tl.c0[l] = 0;
-      for (const MatRef* m : all) tl.c0[l] += m->width;
-      while (next < sorted.size() && sorted[next]->height == nlen) all.push_back(sorted[next++]);
-      tl.c1[l] = 0;
-      for (const MatRef* m : all) tl.c1[l] += m->width;
+      top_layer_cols(tl, l, all, sorted, next, nlen);
       t.layers[L + l].reset(8 * nlen);
       tl.out[l] = t.layers[L + l].p;
     }

@@ -74,7 +74,9 @@ KB_HD uint32_t cube(uint32_t x) {
 // [[2,3,1,1],[1,2,3,1],[1,1,2,3],[3,1,1,2]] per 4-element block, then each element gets the
 // sum of the 4 blocks at its position.  A row's coefficients sum to 35.
 constexpr uint32_t C32 = (1u << 25) - 2;  // 2^32 mod p
-KB_HD void mds_light64(uint64_t s[16]) {
+// The M4 blocks and the four block sums; element i of the layer's output is s[i] + sums[i & 3]
+// (left to the caller, so that a permutation's last layer finishes only the elements read).
+KB_HD void mds_light64_blocks(uint64_t s[16], uint64_t sums[4]) {
 #pragma unroll
   for (int b = 0; b < 16; b += 4) {
     const uint64_t x0 = s[b], x1 = s[b + 1], x2 = s[b + 2], x3 = s[b + 3];
@@ -85,9 +87,12 @@ KB_HD void mds_light64(uint64_t s[16]) {
     s[b + 0] = t01123 + t01;        // 2x0 + 3x1 + x2 + x3
     s[b + 2] = t01233 + t23;        // x0 + x1 + 2x2 + 3x3
   }
-  uint64_t sums[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) sums[k] = (s[k] + s[4 + k]) + (s[8 + k] + s[12 + k]);
+}
+KB_HD void mds_light64(uint64_t s[16]) {
+  uint64_t sums[4];
+  mds_light64_blocks(s, sums);
 #pragma unroll
   for (int i = 0; i < 16; i++) s[i] += sums[i & 3];
 }
@@ -278,8 +283,9 @@ KB_HD int64_t fold_s(int64_t u) {
 // External rounds with the constants already in front of the MDS layers (P2Pre): a[i] are the
 // first round's S-box inputs (constant included); round r's S-box output gets K[r] (the M^-1
 // image of the constant the reduction after its MDS would add).  Leaves the 4th MDS output
-// (64-bit R^2-form) in y.
-KB_HD void external_rounds_pre(const int32_t a[16], int64_t y[16], const int32_t (&K)[4][16]) {
+// (64-bit R^2-form) in y; with sums given, that output is y[i] + sums[i & 3], not yet added.
+KB_HD void external_rounds_pre(const int32_t a[16], int64_t y[16], const int32_t (&K)[4][16],
+                               uint64_t* sums = nullptr) {
   uint64_t* u = reinterpret_cast<uint64_t*>(y);
 #pragma unroll
   for (int r = 0; r < 4; r++) {
@@ -289,18 +295,48 @@ KB_HD void external_rounds_pre(const int32_t a[16], int64_t y[16], const int32_t
       const int64_t c3 = (int64_t)mred_s((int64_t)x * x) * x + K[r][i];
       y[i] = fold_s(c3);
     }
-    mds_light64(u);
+    if (r == 3 && sums) mds_light64_blocks(u, sums);
+    else mds_light64(u);
   }
 }
-KB_HD void poseidon2_permute(uint32_t s[16]) {
+// A permutation is prologue + core + epilogue.  The core is the bulk (all 21 rounds); the ends
+// are small, so a kernel that knows more about a state than "16 words in, 16 words out" picks
+// cheaper ends around one shared inlined core (poseidon2_permute_ends, merkle.hip).
+//
+// Prologue: the initial MDS-light on x R^2 + M^-1 rc_0 (s C32 < 2^56, rows sum to 35: < 2^61.2),
+// reduced to the first round's S-box inputs.
+KB_HD void p2_prologue(const uint32_t s[16], int32_t t[16]) {
   int64_t y[16];
-  int32_t t[16];
-  // initial MDS-light on x R^2 + M^-1 rc_0 (s C32 < 2^56, rows sum to 35: < 2^61.2)
 #pragma unroll
   for (int i = 0; i < 16; i++) y[i] = (int64_t)((uint64_t)s[i] * C32) + P2PRE.init0[i];
   mds_light64(reinterpret_cast<uint64_t*>(y));
 #pragma unroll
   for (int i = 0; i < 16; i++) t[i] = mred_s(y[i]);
+}
+// The same with s[8..16) known to be zero (a sponge's first permutation; s[8..16) is not read):
+// those products are gone and the M4 blocks of the constants fold at compile time.
+KB_HD void p2_prologue_cap0(const uint32_t s[16], int32_t t[16]) {
+  int64_t y[16];
+#pragma unroll
+  for (int i = 0; i < 8; i++) y[i] = (int64_t)((uint64_t)s[i] * C32) + P2PRE.init0[i];
+#pragma unroll
+  for (int i = 8; i < 16; i++) y[i] = P2PRE.init0[i];
+  mds_light64(reinterpret_cast<uint64_t*>(y));
+#pragma unroll
+  for (int i = 0; i < 16; i++) t[i] = mred_s(y[i]);
+}
+// Epilogue: the last MDS-light's block-sum add, the reduction and the correction to [0, p), for
+// elements [I0, I1) only; the others keep what s held before.
+template <int I0, int I1>
+KB_HD void p2_epilogue(uint32_t s[16], const int64_t y[16], const uint64_t sums[4]) {
+#pragma unroll
+  for (int i = I0; i < I1; i++) {
+    const uint32_t r = (uint32_t)mred_s((int64_t)((uint64_t)y[i] + sums[i & 3]));
+    s[i] = umin(r, r + P);
+  }
+}
+// Core: t = the first round's S-box inputs; leaves the last MDS-light as y and sums.
+KB_HD void p2_core(int32_t t[16], int64_t y[16], uint64_t sums[4]) {
   external_rounds_pre(t, y, P2PRE.init);
 #pragma unroll
   for (int i = 0; i < 16; i++) t[i] = mred_s(y[i]);  // rc_int[0] already in y[0]
@@ -348,11 +384,47 @@ KB_HD void poseidon2_permute(uint32_t s[16]) {
       t[5] = mred_s((int64_t)P2M.dd[5] * mred_s(u5) + (q + P2S.rc_term[0][5]));
     }
   }
-  external_rounds_pre(t, y, P2PRE.term);
+  external_rounds_pre(t, y, P2PRE.term, sums);
+}
+KB_HD void poseidon2_permute(uint32_t s[16]) {
+  int64_t y[16];
+  uint64_t sums[4];
+  int32_t t[16];
+  p2_prologue(s, t);
+  p2_core(t, y, sums);
+  p2_epilogue<0, 16>(s, y, sums);
+}
+// A word that nobody reads (a register as it stands, no instruction).
+KB_HD uint32_t unread_word() {
+  uint32_t x = 0;
+#ifdef __HIP_DEVICE_COMPILE__
+  asm volatile("" : "=v"(x));
+#endif
+  return x;
+}
+// One permutation with the ends chosen at run time (wave-uniform flags): cap0 = s[8..16) is
+// zero on entry; lo / hi = finish s[0..8) / s[8..16).  An unfinished half holds unspecified
+// words afterwards (keeping the old ones would keep them live across the core).
+// The core is inlined once however the flags vary, which is what keeps a kernel that permutes
+// in a loop at one copy of it.
+KB_HD void poseidon2_permute_ends(uint32_t s[16], bool cap0, bool lo, bool hi) {
+  int64_t y[16];
+  uint64_t sums[4];
+  int32_t t[16];
+  if (cap0) p2_prologue_cap0(s, t);
+  else p2_prologue(s, t);
+  p2_core(t, y, sums);
+  if (lo) {
+    p2_epilogue<0, 8>(s, y, sums);
+  } else {
 #pragma unroll
-  for (int i = 0; i < 16; i++) {
-    const uint32_t r = (uint32_t)mred_s(y[i]);
-    s[i] = umin(r, r + P);
+    for (int i = 0; i < 8; i++) s[i] = unread_word();
+  }
+  if (hi) {
+    p2_epilogue<8, 16>(s, y, sums);
+  } else {
+#pragma unroll
+    for (int i = 8; i < 16; i++) s[i] = unread_word();
   }
 }
 // ---------------------------------------------------------------------------------------
