@@ -227,6 +227,16 @@ pub struct bfz_debug_report {
     pub kind_count: [[u32; BFZ_NUM_CHIPS]; BFZ_NUM_KINDS],
 }
 
+/// One proof's verdict from `bfz_verify_batch` (`StarkMachine::verify`, machine.rs:258-284):
+/// `why` is a NUL-terminated reason, empty when `ok == 1`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bfz_verify_outcome {
+    pub ok: i32,
+    pub query: i32,
+    pub why: [c_char; 120],
+}
+
 pub type bfz_allgather_fn =
     Option<unsafe extern "C" fn(ctx: *mut c_void, send: *const c_void, bytes: usize, recv: *mut c_void) -> c_int>;
 pub type bfz_allreduce_u32_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, data: *mut u32, n: usize) -> c_int>;
@@ -290,6 +300,9 @@ extern "C" {
                             proof: *mut *mut u8, proof_len: *mut usize) -> c_int;
     pub fn bfz_verify(elf: *const c_char, vk_commit: *const u32, proof: *const u8,
                       proof_len: usize) -> c_int;
+    pub fn bfz_verify_batch(elf: *const c_char, vk_commit: *const u32, proofs: *const *const u8,
+                            lens: *const usize, n: usize, on_device: c_int,
+                            out: *mut bfz_verify_outcome) -> c_int;
     pub fn bfz_prove_batch(pk: *const bfz_pk, stdins: *const *const u8, nins: *const usize,
                            njobs: usize, exec_threads: c_int, proofs: *mut *mut u8,
                            proof_lens: *mut usize, stats: *mut bfz_batch_stats) -> c_int;

@@ -194,6 +194,25 @@ int bfz_prove_traces(const bfz_pk* pk, const int* chips, const uint32_t* const* 
 int bfz_verify(const char* elf, const uint32_t vk_commit[8], const uint8_t* proof,
                size_t proof_len);
 
+/* StarkMachine::verify (crates/stark/src/machine.rs:258-284) of n proofs of one program.
+ * on_device = 0: the host verifier, proof by proof.  1: the query phase of all n proofs (the
+ * Merkle openings of the four input rounds and of every FRI commit-phase step, the reduced
+ * openings and the fold chain: nearly all of a verification's Poseidon2 permutations) in one
+ * batched device pass; decoding, the transcript replay, the PoW check, the out-of-domain check
+ * and the cumulative-sum check stay on the host.  Both give the same outcome for the same bytes:
+ * `why` is the host verifier's reason (truncated to 119 characters), the first failure in its
+ * order.  Returns 0 whenever the check RAN (as the constraint checker does), whatever the
+ * outcomes; negative for a real error (NULL arguments, no device bound with on_device = 1, a
+ * device error).  n = 0 is a successful no-op.  Honours bfz_set_num_queries and
+ * bfz_set_pcs_variant exactly as bfz_verify does. */
+typedef struct {
+  int32_t ok;    /* 1 accepted, 0 rejected */
+  int32_t query; /* the query whose check failed first, -1 if the rejection is not a query's */
+  char why[120]; /* "" when ok; otherwise the host verifier's reason string */
+} bfz_verify_outcome;
+int bfz_verify_batch(const char* elf, const uint32_t vk_commit[8], const uint8_t* const* proofs,
+                     const size_t* lens, size_t n, int on_device, bfz_verify_outcome* out);
+
 /* Pipelined proofs of one program over many inputs (the reference's execute-then-prove loop,
  * crates/core/machine/src/utils/prove.rs:23-66, with execution off the critical path):
  * exec_threads host threads run the executor into pinned memory, a copy stream uploads job
@@ -487,7 +506,11 @@ int bfz_set_pcs_variant(int observe_openings);
 
 /* Test-only fault injection, no reference counterpart: bit 0 perturbs the device challenger's
  * uploaded sponge state, so the host's replay of the device-sampled challenges must fail the
- * proof with "device transcript diverged" (tests/test_gpu.py).  0 (default) = off. */
+ * proof with "device transcript diverged" (tests/test_gpu.py).  Bit 1 makes bfz_verify_batch with
+ * on_device = 1 run its host side only (stages, packing, the queries the packing keeps on the
+ * host) with a stand-in for the kernels that reports no failure and needs no device, so that side
+ * is testable without a GPU (tests/test_verify_batch.py); its verdicts are then not a
+ * verification.  0 (default) = off. */
 int bfz_set_fault_injection(int mask);
 
 /* Proof wire format.  bfz_prove* return the BFZ1 normal form; bfz_proof_to_bincode turns it

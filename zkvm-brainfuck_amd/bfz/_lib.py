@@ -71,6 +71,11 @@ class DebugReportC(ctypes.Structure):
                 ("kind_count", (c_uint32 * NUM_CHIPS) * NUM_KINDS)]
 
 
+class VerifyOutcomeC(ctypes.Structure):
+    """bfz_verify_outcome: one proof's verdict from bfz_verify_batch."""
+    _fields_ = [("ok", c_int32), ("query", c_int32), ("why", ctypes.c_char * 120)]
+
+
 class Events(ctypes.Structure):
     """bfz_events: the reference ExecutionRecord's event arrays (pointers to bfz_*_event arrays,
     see bfz/events.py for their numpy layouts)."""
@@ -138,6 +143,8 @@ SIGNATURES = [
                                 c_int, POINTER(POINTER(c_uint8)), POINTER(c_size_t),
                                 POINTER(BatchStats)]),
     ("bfz_verify", c_int, [c_char_p, POINTER(c_uint32), POINTER(c_uint8), c_size_t]),
+    ("bfz_verify_batch", c_int, [c_char_p, POINTER(c_uint32), POINTER(POINTER(c_uint8)),
+                                 POINTER(c_size_t), c_size_t, c_int, POINTER(VerifyOutcomeC)]),
     ("bfz_record_new", c_int, [c_void_p, POINTER(c_uint8), c_size_t, POINTER(c_void_p),
                                POINTER(c_uint64)]),
     ("bfz_record_prove", c_int, [c_void_p, c_void_p, POINTER(POINTER(c_uint8)), POINTER(c_size_t),
@@ -239,5 +246,5 @@ def take_bytes(ptr, n: int) -> bytes:
 
 
 __all__ = ["lib", "check", "init", "u8buf", "take_bytes", "BfzError", "Timings", "Events", "LIB_PATH",
-           "ChipCheck", "DebugReportC",
+           "ChipCheck", "DebugReportC", "VerifyOutcomeC",
            "SIGNATURES", "byref"]

@@ -119,6 +119,15 @@ class BfProofWithPublicValues:
         raise BfzError("not a bincode BfProofWithPublicValues")
 
 
+@dataclass
+class VerifyOutcome:
+    """bfz_verify_outcome: ok, the query whose check failed first (-1 if the rejection is not a
+    query's) and the host verifier's reason ("" when ok)."""
+    ok: bool
+    query: int
+    why: str
+
+
 class Execute:
     """action::Execute (crates/sdk/src/action.rs:10-33)."""
 
@@ -202,10 +211,38 @@ class ProverClient:
             public_values=Execute(pk.elf, x).run() if public_values else b"")
             for pf, x in zip(proofs, ins)]
 
-    def verify(self, proof: BfProofWithPublicValues, vk: BfVerifyingKey) -> None:
+    def verify(self, proof: BfProofWithPublicValues, vk: BfVerifyingKey,
+               on_device: bool = False) -> None:
+        """ProverClient::verify (lib.rs:110-116).  on_device=True runs the query phase on the GPU
+        (bfz_verify_batch); the verdict and the reason of a rejection are the host verifier's."""
+        if on_device:
+            o = self.verify_batch([proof], vk, on_device=True)[0]
+            if not o.ok:
+                raise BfzError(f"verification failed: {o.why}")
+            return
         buf, n = u8buf(proof.proof)
         commit = (ctypes.c_uint32 * 8)(*vk.commit)
         check(lib().bfz_verify(vk.elf.encode(), commit, buf, n))
+
+    def verify_batch(self, proofs, vk: BfVerifyingKey, on_device: bool = True) -> List[VerifyOutcome]:
+        """StarkMachine::verify (crates/stark/src/machine.rs:258-284) of many proofs of vk's
+        program (bfz_verify_batch): BfProofWithPublicValues or BFZ1 bytes.  A rejected proof does
+        not raise; its outcome says which query failed first (if one did) and why.
+        on_device=True checks every proof's query phase in one batched GPU pass; False runs the
+        host verifier proof by proof.  Both give the same outcomes."""
+        if on_device:
+            init(self.device)
+        raw = [bytes(p.proof if isinstance(p, BfProofWithPublicValues) else p) for p in proofs]
+        k = len(raw)
+        bufs = [u8buf(x) for x in raw]
+        arr = (ctypes.POINTER(ctypes.c_uint8) * max(k, 1))(
+            *[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b, _ in bufs])
+        lens = (ctypes.c_size_t * max(k, 1))(*[n for _, n in bufs])
+        out = (_lib.VerifyOutcomeC * max(k, 1))()
+        commit = (ctypes.c_uint32 * 8)(*vk.commit)
+        check(lib().bfz_verify_batch(vk.elf.encode(), commit, arr, lens, k, int(bool(on_device)), out))
+        return [VerifyOutcome(ok=bool(out[i].ok), query=out[i].query, why=out[i].why.decode())
+                for i in range(k)]
 
     def verify_bincode(self, shard_proof: bytes, vk: BfVerifyingKey,
                        field_repr: int = FIELD_MONTGOMERY) -> None:

@@ -26,6 +26,7 @@
 #include "prover.h"
 #include "tracegen.h"
 #include "verifier.h"
+#include "verify.h"
 
 struct bfz_pk {
   std::shared_ptr<const bfz::ProvingKey> pk;  // shared with the per-program setup cache
@@ -64,6 +65,7 @@ std::unordered_map<void*, std::vector<uint8_t>*>& emitted() {
 int g_num_queries = -1;
 int g_observe_openings = -1;  // -1: BFZ_OBSERVE_OPENINGS / default
 int g_fault = 0;              // bfz_set_fault_injection (tests only)
+int g_bound = -1;             // the device bfz_init bound this process to
 
 int fail(const std::exception& e, int code = -1) {
   g_err = e.what();
@@ -98,7 +100,7 @@ extern "C" {
 // caches and the pinned staging arena are process-wide and belong to the first device bound.
 int bfz_init(int device) {
   return guarded([&] {
-    static int bound = -1;
+    int& bound = g_bound;
     int n = 0;
     HIP_CHECK(hipGetDeviceCount(&n));
     if (n <= 0) throw std::runtime_error("no HIP device");
@@ -825,6 +827,39 @@ int bfz_verify(const char* elf, const uint32_t vk_commit[8], const uint8_t* proo
   });
 }
 
+int bfz_verify_batch(const char* elf, const uint32_t vk_commit[8], const uint8_t* const* proofs,
+                     const size_t* lens, size_t n, int on_device, bfz_verify_outcome* out) {
+  return guarded([&] {
+    if (!elf || !vk_commit) throw std::runtime_error("null argument");
+    if (n == 0) return 0;
+    if (!proofs || !lens || !out) throw std::runtime_error("null argument");
+    for (size_t i = 0; i < n; i++)
+      if (!proofs[i] && lens[i]) throw std::runtime_error("null proof");
+    const bool standin = on_device && (g_fault & 2);  // bfz_set_fault_injection bit 1 (tests only)
+    if (on_device && !standin && g_bound < 0)
+      throw std::runtime_error("verify_batch: no device bound (bfz_init) for on_device = 1");
+    const bfz::ProveOptions o = opts();
+    bfz::VerifyOptions vo;
+    vo.num_queries = o.num_queries;
+    vo.observe_openings = o.observe_openings;
+    const bfz::QueryRunner run = [](const bfz::QueryBatch& b, uint32_t* keys) {
+      bfz::verify_queries_device(b, keys, bfz::stream());
+    };
+    // the stand-in runs no kernel and leaves every key at "no failure": what remains is the host
+    // side of the device path (stages, packing, the queries the packing keeps on the host)
+    const bfz::QueryRunner none = [](const bfz::QueryBatch&, uint32_t*) {};
+    const std::vector<bfz::VerifyOutcome> v =
+        bfz::verify_batch(elf, vk_commit, proofs, lens, n, vo, standin ? none : on_device ? run : nullptr);
+    for (size_t i = 0; i < n; i++) {
+      std::memset(&out[i], 0, sizeof out[i]);
+      out[i].ok = v[i].ok;
+      out[i].query = v[i].query;
+      std::snprintf(out[i].why, sizeof out[i].why, "%s", v[i].why.c_str());
+    }
+    return 0;
+  });
+}
+
 int bfz_record_new(const bfz_pk* pk, const uint8_t* in, size_t nin, bfz_record** rec,
                    uint64_t* cycles) {
   return guarded([&] {
@@ -1406,7 +1441,7 @@ int bfz_set_pcs_variant(int observe_openings) {
 
 int bfz_set_fault_injection(int mask) {
   return guarded([&] {
-    if (mask & ~1) throw std::runtime_error("fault mask: bit 0 (device challenger) only");
+    if (mask & ~3) throw std::runtime_error("fault mask: bits 0 (device challenger) and 1 (verifier kernels stand-in) only");
     g_fault = mask;
     return 0;
   });

@@ -18,6 +18,7 @@
 #include "machine.h"
 #include "poseidon2.h"
 #include "prover.h"
+#include "verify.h"
 
 namespace bfz {
 
@@ -145,23 +146,35 @@ EF zp_at(int log_n, uint32_t shift, const EF& x) {  // (x / s)^(2^log_n) - 1
 // number of byte lookups each chip SENDS (Chip::num_sent_byte_lookups)
 int sent_byte_lookups(int chip) { return chip == CHIP_CPU ? 7 : chip == CHIP_ADDSUB ? 3 : 0; }
 
-}  // namespace
+// verify_shard in three stages that share this state: before_queries (everything up to the query
+// loop: shapes, transcript replay, PoW, the query indices), check_query (one turn of the query
+// loop) and after_queries (the OOD and cumulative-sum checks).  Each throws the reason of the first
+// check that fails.  The state refers into the proof, which must outlive it.
+struct ChipOpen {
+  int log_n;
+  const std::vector<EF> &pl, &pn, &ml, &mn, &perml, &permn;
+  const std::vector<EF>* q;
+  EF cumsum;
+};
+struct VMat { int log_n; uint32_t shift; int w; int np; EF pt[2]; const std::vector<EF>* v[2]; };
+struct ShardState {
+  const ShardProof* pf = nullptr;
+  std::vector<ChipOpen> co;
+  EF pa, pb, alpha, zeta, fri_alpha, final_poly;
+  std::vector<VMat> rounds[4];
+  const uint32_t* roots[4] = {};
+  std::vector<EF> betas;
+  uint32_t ncommit = 0, nq = 0;
+  int log_max = 0;
+  std::vector<size_t> index;  // the sampled index of every query
+};
 
-bool verify_proof(const std::string& src, const uint32_t vk_commit[8], const uint8_t* proof,
-                  size_t len, const VerifyOptions& opt, std::string* why) {
-  ShardProof pf;
-  try {
-    pf = decode_bfz1(proof, len);
-  } catch (const std::exception& e) {
-    if (why) *why = e.what();
-    return false;
-  }
-  return verify_shard(src, vk_commit, pf, opt, why);
-}
-
-bool verify_shard(const std::string& src, const uint32_t vk_commit[8], const ShardProof& pf,
-                  const VerifyOptions& opt, std::string* why) {
-  try {
+void before_queries(const std::string& src, const uint32_t vk_commit[8], const ShardProof& pf,
+                    const VerifyOptions& opt, ShardState& S) {
+  S.pf = &pf;
+  std::vector<ChipOpen>& co = S.co;
+  std::vector<VMat>* rounds = S.rounds;
+  {
     Program prog = Program::parse(src);
     // vk.chip_information: prep matrices sorted by (Reverse(height), name)
     size_t prog_h = std::max<size_t>(16, [&] {
@@ -188,13 +201,6 @@ bool verify_shard(const std::string& src, const uint32_t vk_commit[8], const Sha
     const uint32_t* main_root = pf.main_root.data();
     const uint32_t* perm_root = pf.perm_root.data();
     const uint32_t* quot_root = pf.quot_root.data();
-    struct ChipOpen {
-      int log_n;
-      const std::vector<EF> &pl, &pn, &ml, &mn, &perml, &permn;
-      const std::vector<EF>* q;
-      EF cumsum;
-    };
-    std::vector<ChipOpen> co;
     co.reserve(nc);
     for (uint32_t i = 0; i < nc; i++) {
       const ChipOpened& o = pf.opened[i];
@@ -238,19 +244,18 @@ bool verify_shard(const std::string& src, const uint32_t vk_commit[8], const Sha
     ch.observe_digest(vk_commit);
     for (int i = 0; i < 7; i++) ch.observe(0);
     ch.observe_digest(main_root);
-    const EF pa = ch.sample_ef(), pb = ch.sample_ef();
+    S.pa = ch.sample_ef();
+    S.pb = ch.sample_ef();
     ch.observe_digest(perm_root);
     for (uint32_t i = 0; i < nc; i++) {
       ch.observe_ef(co[i].cumsum);
       // chips with no interactions must have a zero sum (all chips here have interactions)
     }
-    const EF alpha = ch.sample_ef();
+    S.alpha = ch.sample_ef();
     ch.observe_digest(quot_root);
-    const EF zeta = ch.sample_ef();
+    const EF zeta = S.zeta = ch.sample_ef();
 
     // ---- rounds for PCS verify
-    struct VMat { int log_n; uint32_t shift; int w; int np; EF pt[2]; const std::vector<EF>* v[2]; };
-    std::vector<VMat> rounds[4];
     for (const PrepInfo& pi : prep) {
       int idx = -1;
       for (uint32_t j = 0; j < nc; j++) if (chip[j] == pi.chip) idx = (int)j;
@@ -275,32 +280,51 @@ bool verify_shard(const std::string& src, const uint32_t vk_commit[8], const Sha
         for (const VMat& m : rounds[rr])
           for (int p = 0; p < m.np; p++)
             for (int c = 0; c < m.w; c++) ch.observe_ef((*m.v[p])[c]);
-    const EF fri_alpha = ch.sample_ef();
-    const uint32_t ncommit = (uint32_t)pf.commit_roots.size();
+    S.fri_alpha = ch.sample_ef();
+    const uint32_t ncommit = S.ncommit = (uint32_t)pf.commit_roots.size();
     if (ncommit > 30) throw std::runtime_error("too many FRI rounds");
-    const int log_max = (int)ncommit + LOG_BLOWUP;
+    const int log_max = S.log_max = (int)ncommit + LOG_BLOWUP;
     {  // the commit phase folds the tallest LDE down to 2^LOG_BLOWUP: every height must fit
       int lh_max = 0;
       for (int rr = 0; rr < 4; rr++)
         for (const VMat& m : rounds[rr]) lh_max = std::max(lh_max, m.log_n + LOG_BLOWUP);
       if (lh_max != log_max) throw std::runtime_error("FRI round count does not match the tallest matrix");
     }
-    std::vector<EF> betas(ncommit);
+    S.betas.resize(ncommit);
     for (uint32_t i = 0; i < ncommit; i++) {
       ch.observe_digest(pf.commit_roots[i].data());
-      betas[i] = ch.sample_ef();
+      S.betas[i] = ch.sample_ef();
     }
-    const uint32_t nq = (uint32_t)pf.queries.size();
+    const uint32_t nq = S.nq = (uint32_t)pf.queries.size();
     if ((int)nq != opt.num_queries) throw std::runtime_error("wrong number of queries");
-    const EF final_poly = pf.final_poly;
-    ch.observe_ef(final_poly);
+    S.final_poly = pf.final_poly;
+    ch.observe_ef(S.final_poly);
     if (!ch.check_witness(POW_BITS, from_mont(pf.pow_witness))) throw std::runtime_error("bad PoW witness");
-    const uint32_t* roots[4] = {vk_commit, main_root, perm_root, quot_root};
-    const uint32_t half = to_mont_c((P + 1) / 2);
-    (void)half;
-    for (uint32_t q = 0; q < nq; q++) {
+    S.roots[0] = vk_commit;
+    S.roots[1] = main_root;
+    S.roots[2] = perm_root;
+    S.roots[3] = quot_root;
+    // nothing but the indices is drawn from the transcript from here on, and no check of the
+    // query loop touches it: sampling them all first changes no outcome
+    S.index.resize(nq);
+    for (uint32_t q = 0; q < nq; q++) S.index[q] = ch.sample_bits(log_max);
+  }
+}
+
+// One turn of the query loop: the four input openings with their reduced openings, then
+// verify_query (the fold chain with one commit-phase opening per step).
+void check_query(const ShardState& S, uint32_t q) {
+  const ShardProof& pf = *S.pf;
+  const std::vector<VMat>* rounds = S.rounds;
+  const uint32_t* const* roots = S.roots;
+  const EF fri_alpha = S.fri_alpha, final_poly = S.final_poly;
+  const std::vector<EF>& betas = S.betas;
+  const uint32_t ncommit = S.ncommit;
+  const int log_max = S.log_max;
+  {
+    {
       const QueryProof& qp = pf.queries[q];
-      const size_t index = ch.sample_bits(log_max);
+      const size_t index = S.index[q];
       if (qp.inputs.size() != 4) throw std::runtime_error("bad round count");
       std::map<int, std::pair<EF, EF>> ro;  // log height -> (alpha_pow, ro)
       for (int rr = 0; rr < 4; rr++) {
@@ -381,7 +405,16 @@ bool verify_shard(const std::string& src, const uint32_t vk_commit[8], const Sha
       if (!ro.empty()) throw std::runtime_error("unconsumed reduced openings");
       if (!ef_eq(folded, final_poly)) throw std::runtime_error("FRI final value mismatch");
     }
+  }
+}
 
+void after_queries(const ShardState& S) {
+  const ShardProof& pf = *S.pf;
+  const std::vector<int>& chip = pf.chips;
+  const std::vector<ChipOpen>& co = S.co;
+  const uint32_t nc = (uint32_t)chip.size();
+  const EF pa = S.pa, pb = S.pb, alpha = S.alpha, zeta = S.zeta;
+  {
     // ---- OOD constraint checks (verifier.rs:194-213)
     EF total = ef_zero();
     for (uint32_t i = 0; i < nc; i++) {
@@ -424,11 +457,314 @@ bool verify_shard(const std::string& src, const uint32_t vk_commit[8], const Sha
       total = ef_add(total, c.cumsum);
     }
     if (!ef_is_zero(total)) throw std::runtime_error("cumulative sums do not sum to zero");
-    return true;
+  }
+}
+
+// The three stages in order, as the reference runs them; *query follows the query loop.
+VerifyOutcome run_host(const std::string& src, const uint32_t vk_commit[8], const ShardProof& pf,
+                       const VerifyOptions& opt) {
+  VerifyOutcome o;
+  try {
+    ShardState S;
+    before_queries(src, vk_commit, pf, opt, S);
+    for (uint32_t q = 0; q < S.nq; q++) {
+      o.query = (int)q;
+      check_query(S, q);
+    }
+    o.query = -1;
+    after_queries(S);
+    o.ok = true;
+  } catch (const std::exception& e) {
+    o.why = e.what();
+  }
+  return o;
+}
+
+// ------------------------------------------------------------------ packing for the device
+// The per-query shape checks of check_query, in its order; false at the first that would throw.
+bool query_shape_ok(const ShardState& S, const QueryProof& qp) {
+  if (qp.inputs.size() != 4) return false;
+  for (int rr = 0; rr < 4; rr++) {
+    const BatchOpening& bo = qp.inputs[rr];
+    if (bo.rows.size() != S.rounds[rr].size()) return false;
+    int lbmax = 0;
+    for (size_t i = 0; i < bo.rows.size(); i++) {
+      if ((int)bo.rows[i].size() != S.rounds[rr][i].w) return false;
+      lbmax = std::max(lbmax, S.rounds[rr][i].log_n + LOG_BLOWUP);
+    }
+    if ((int)bo.path.size() != lbmax) return false;
+  }
+  if (qp.steps.size() != S.ncommit) return false;
+  for (uint32_t s = 0; s < S.ncommit; s++)
+    if ((int)qp.steps[s].path.size() != S.log_max - 1 - (int)s) return false;
+  return true;
+}
+
+void put_ef(std::vector<uint32_t>& w, const EF& e) { w.insert(w.end(), e.c, e.c + 4); }
+
+// Appends one proof to the batch: its descriptor (slot `slot`) and its data.  Queries
+// [0, first_bad) have the shapes the descriptor states and are packed; *first_bad == nq if all do.
+// Every offset and length the kernels use is computed here from S (the program, the vk and the
+// chips' validated log degrees), never taken from a query's own vectors.
+void pack_proof(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* first_bad) {
+  const ShardProof& pf = *S.pf;
+  uint32_t nq = 0;
+  while (nq < S.nq && query_shape_ok(S, pf.queries[nq])) nq++;
+  *first_bad = nq;
+  VProof D;
+  std::memset(&D, 0, sizeof D);
+  D.nq = nq;
+  D.log_max = (uint32_t)S.log_max;
+  D.ncommit = S.ncommit;
+  D.final_poly = S.final_poly;
+  if (S.log_max < 1 || S.log_max > 24) throw std::runtime_error("verify_batch: log height out of range");
+  std::vector<uint32_t>& W = B.words;
+
+  // the record of one query: per round the rows in Merkle order and the path, then the steps
+  uint32_t rec = 0;
+  std::vector<int> ord[4];                  // Merkle order of each round's matrices
+  std::vector<uint32_t> mat_off[4];         // record offset of matrix i's row
+  for (int rr = 0; rr < 4; rr++) {
+    const std::vector<VMat>& ms = S.rounds[rr];
+    ord[rr].resize(ms.size());
+    for (size_t i = 0; i < ms.size(); i++) ord[rr][i] = (int)i;
+    std::stable_sort(ord[rr].begin(), ord[rr].end(),
+                     [&](int a, int b) { return ms[a].log_n > ms[b].log_n; });
+    VRoundD& R = D.rd[rr];
+    R.rows_off = rec;
+    mat_off[rr].resize(ms.size());
+    for (int i : ord[rr]) {
+      const VMat& m = ms[i];
+      if (m.w < 1 || m.w > VQ_MAX_WIDTH) throw std::runtime_error("verify_batch: row width out of range");
+      const uint32_t lh = (uint32_t)(m.log_n + LOG_BLOWUP);
+      if (R.ngroups == 0 || R.g_lh[R.ngroups - 1] != lh) {
+        if (R.ngroups == VQ_MAX_HEIGHTS) throw std::runtime_error("verify_batch: too many heights");
+        R.g_lh[R.ngroups] = lh;
+        R.g_w[R.ngroups] = 0;
+        R.ngroups++;
+      }
+      R.g_w[R.ngroups - 1] += (uint32_t)m.w;
+      mat_off[rr][i] = rec;
+      rec += (uint32_t)m.w;
+    }
+    R.lb = R.g_lh[0];
+    R.path_off = rec;
+    rec += 8 * R.lb;
+    std::memcpy(R.root, S.roots[rr], 32);
+  }
+  D.steps_off = rec;
+  for (uint32_t s = 0; s < S.ncommit; s++) rec += 4 + 8 * (uint32_t)(S.log_max - 1 - (int)s);
+  D.qstride = rec;
+
+  // reduced openings: per LDE height, the matrices in the verifier's order (round, then matrix),
+  // alpha^k running over (matrix, point, column) across the rounds
+  std::vector<int> heights;
+  for (int rr = 0; rr < 4; rr++)
+    for (const VMat& m : S.rounds[rr]) {
+      const int lh = m.log_n + LOG_BLOWUP;
+      if (std::find(heights.begin(), heights.end(), lh) == heights.end()) heights.push_back(lh);
+    }
+  if (heights.size() > (size_t)VQ_MAX_HEIGHTS) throw std::runtime_error("verify_batch: too many heights");
+  D.nheights = (uint32_t)heights.size();
+  for (size_t j = 0; j < heights.size(); j++) {
+    VHeightD& H = D.hs[j];
+    H.lh = (uint32_t)heights[j];
+    H.m0 = D.nmats;
+    H.a0 = H.a1 = ef_zero();
+    H.z0 = S.zeta;
+    H.z1 = ef_mul_base(S.zeta, two_adic_gen(heights[j] - LOG_BLOWUP));
+    EF apow = ef_one();
+    for (int rr = 0; rr < 4; rr++)
+      for (size_t i = 0; i < S.rounds[rr].size(); i++) {
+        const VMat& m = S.rounds[rr][i];
+        if (m.log_n + LOG_BLOWUP != heights[j]) continue;
+        if (D.nmats == (uint32_t)VQ_MAX_MATS) throw std::runtime_error("verify_batch: too many matrices");
+        VMatD& M = D.mats[D.nmats++];
+        M.off = mat_off[rr][i];
+        M.w = (uint32_t)m.w;
+        M.np = (uint32_t)m.np;
+        M.c0 = M.c1 = ef_zero();
+        for (int p = 0; p < m.np; p++) {
+          // every point of this height is zeta or zeta * g (the quotient chunks: zeta only)
+          const bool second = p == 1;
+          if (!ef_eq(m.pt[p], second ? H.z1 : H.z0)) throw std::runtime_error("verify_batch: unexpected opening point");
+          (second ? M.c1 : M.c0) = apow;
+          EF& a = second ? H.a1 : H.a0;
+          for (int c = 0; c < m.w; c++) {
+            a = ef_add(a, ef_mul(apow, (*m.v[p])[c]));
+            apow = ef_mul(apow, S.fri_alpha);
+          }
+        }
+      }
+    H.m1 = D.nmats;
+  }
+
+  // data
+  D.idx_off = (uint32_t)W.size();
+  for (uint32_t q = 0; q < nq; q++) W.push_back((uint32_t)S.index[q]);
+  D.croot_off = (uint32_t)W.size();
+  for (uint32_t s = 0; s < S.ncommit; s++) W.insert(W.end(), pf.commit_roots[s].begin(), pf.commit_roots[s].end());
+  D.beta_off = (uint32_t)W.size();
+  for (uint32_t s = 0; s < S.ncommit; s++) put_ef(W, S.betas[s]);
+  D.apow_off = (uint32_t)W.size();
+  {
+    EF a = ef_one();
+    for (int c = 0; c < VQ_MAX_WIDTH; c++, a = ef_mul(a, S.fri_alpha)) put_ef(W, a);
+  }
+  D.qbase = (uint32_t)W.size();
+  for (uint32_t q = 0; q < nq; q++) {
+    const QueryProof& qp = pf.queries[q];
+    for (int rr = 0; rr < 4; rr++) {
+      const BatchOpening& bo = qp.inputs[rr];
+      for (int i : ord[rr]) W.insert(W.end(), bo.rows[i].begin(), bo.rows[i].end());
+      for (const Digest& d : bo.path) W.insert(W.end(), d.begin(), d.end());
+    }
+    for (const CommitPhaseStep& st : qp.steps) {
+      put_ef(W, st.sibling);
+      for (const Digest& d : st.path) W.insert(W.end(), d.begin(), d.end());
+    }
+    if (W.size() != (size_t)D.qbase + (size_t)(q + 1) * D.qstride)
+      throw std::runtime_error("verify_batch: query record length mismatch");
+  }
+  if (W.size() >= ((size_t)1 << 31)) throw std::runtime_error("verify_batch: batch too large");
+  D.leaf_base = (uint32_t)B.leaf_words;
+  B.leaf_words += (size_t)nq * S.ncommit * 8;
+  D.ro_base = (uint32_t)B.ro_words;
+  B.ro_words += (size_t)nq * VQ_RO_SLOTS * 4;
+  B.max_nq = std::max(B.max_nq, nq);
+  B.max_ncommit = std::max(B.max_ncommit, S.ncommit);
+  std::memcpy(&W[B.desc_off() + (size_t)slot * (sizeof(VProof) / 4)], &D, sizeof D);
+}
+
+const char* reason_of_stage(uint32_t stage) {
+  if (stage < (uint32_t)VQ_STAGE_STEP0) return "input Merkle opening rejected";
+  if (stage < (uint32_t)VQ_STAGE_FINAL) return "FRI commit-phase opening rejected";
+  return "FRI final value mismatch";
+}
+
+}  // namespace
+
+bool verify_proof(const std::string& src, const uint32_t vk_commit[8], const uint8_t* proof,
+                  size_t len, const VerifyOptions& opt, std::string* why) {
+  ShardProof pf;
+  try {
+    pf = decode_bfz1(proof, len);
   } catch (const std::exception& e) {
     if (why) *why = e.what();
     return false;
   }
+  return verify_shard(src, vk_commit, pf, opt, why);
+}
+
+bool verify_shard(const std::string& src, const uint32_t vk_commit[8], const ShardProof& pf,
+                  const VerifyOptions& opt, std::string* why) {
+  const VerifyOutcome o = run_host(src, vk_commit, pf, opt);
+  if (!o.ok && why) *why = o.why;
+  return o.ok;
+}
+
+std::vector<VerifyOutcome> verify_batch(const std::string& src, const uint32_t vk_commit[8],
+                                        const uint8_t* const* proofs, const size_t* lens, size_t n,
+                                        const VerifyOptions& opt, QueryRunner run_queries) {
+  std::vector<VerifyOutcome> out(n);
+  if (!run_queries) {  // one proof decoded at a time, as bfz_verify
+    for (size_t i = 0; i < n; i++) {
+      try {
+        const ShardProof pf = decode_bfz1(proofs[i], lens[i]);
+        out[i] = run_host(src, vk_commit, pf, opt);
+      } catch (const std::exception& e) {
+        out[i].why = e.what();
+      }
+    }
+    return out;
+  }
+  // the device pass takes the proofs in chunks that bound the packed batch (2^31 words at most)
+  constexpr size_t CHUNK_PROOFS = 1024, CHUNK_BYTES = (size_t)512 << 20;
+  for (size_t i0 = 0; i0 < n;) {
+    size_t i1 = i0, bytes = 0;
+    while (i1 < n && i1 - i0 < CHUNK_PROOFS && (i1 == i0 || bytes + lens[i1] <= CHUNK_BYTES)) bytes += lens[i1++];
+    const size_t k = i1 - i0;
+    std::vector<ShardProof> pfs(k);
+    std::vector<bool> decoded(k, false);
+    for (size_t j = 0; j < k; j++) {
+      try {
+        pfs[j] = decode_bfz1(proofs[i0 + j], lens[i0 + j]);
+        decoded[j] = true;
+      } catch (const std::exception& e) {
+        out[i0 + j].why = e.what();
+      }
+    }
+    // stage one on the host; the survivors are packed
+    std::vector<ShardState> st(k);
+    std::vector<int> slot_of(k, -1);
+    std::vector<size_t> packed;
+    for (size_t j = 0; j < k; j++) {
+      if (!decoded[j]) continue;
+      try {
+        before_queries(src, vk_commit, pfs[j], opt, st[j]);
+        slot_of[j] = (int)packed.size();
+        packed.push_back(j);
+      } catch (const std::exception& e) {
+        out[i0 + j].why = e.what();
+      }
+    }
+    QueryBatch B;
+    B.nproofs = (uint32_t)packed.size();
+    B.words.assign(B.desc_off() + packed.size() * (sizeof(VProof) / 4), 0);
+    for (uint32_t s = 0; s < B.nproofs; s++) B.words[s] = VQ_NO_FAILURE;
+    for (int b = 0; b < 32; b++) {
+      const uint32_t g = b <= 24 ? two_adic_gen(b) : ONE;
+      B.words[B.nproofs + b] = g;
+      B.words[B.nproofs + 32 + b] = minv(g);
+    }
+    std::vector<uint32_t> first_bad(packed.size());
+    for (uint32_t s = 0; s < B.nproofs; s++) {
+      // A proof the packing refuses (before_queries lets through shapes no honest prover makes,
+      // such as a preprocessed chip whose claimed log degree is not its key's: more heights than
+      // the descriptor holds) is that proof's matter, not the call's: its slot stays empty and
+      // all its queries run on the host below, so it gets the host's reason.
+      const uint32_t max_nq = B.max_nq, max_ncommit = B.max_ncommit;
+      const size_t words = B.words.size(), leaf_words = B.leaf_words, ro_words = B.ro_words;
+      try {
+        pack_proof(st[packed[s]], B, s, &first_bad[s]);
+      } catch (const std::exception&) {
+        B.words.resize(words);
+        B.max_nq = max_nq;
+        B.max_ncommit = max_ncommit;
+        B.leaf_words = leaf_words;
+        B.ro_words = ro_words;
+        std::fill_n(&B.words[B.desc_off() + (size_t)s * (sizeof(VProof) / 4)], sizeof(VProof) / 4, 0u);
+        first_bad[s] = 0;
+      }
+    }
+    std::vector<uint32_t> keys(packed.size(), VQ_NO_FAILURE);
+    if (B.max_nq) run_queries(B, keys.data());
+    for (uint32_t s = 0; s < B.nproofs; s++) {
+      const size_t j = packed[s];
+      VerifyOutcome& o = out[i0 + j];
+      const ShardState& S = st[j];
+      if (keys[s] != VQ_NO_FAILURE) {  // the first failure among the packed queries
+        if ((keys[s] >> 6) >= first_bad[s]) throw std::runtime_error("verify_batch: device key out of range");
+        o.query = (int)(keys[s] >> 6);
+        o.why = reason_of_stage(keys[s] & 63);
+        continue;
+      }
+      try {
+        // a query of another shape than the descriptor's, and whatever follows it, stays on the host
+        for (uint32_t q = first_bad[s]; q < S.nq; q++) {
+          o.query = (int)q;
+          check_query(S, q);
+        }
+        o.query = -1;
+        after_queries(S);
+        o.ok = true;
+      } catch (const std::exception& e) {
+        o.why = e.what();
+      }
+    }
+    i0 = i1;
+  }
+  return out;
 }
 
 // Columns a chip's constraints read at the next row (quotient.rs:41-42), found by perturbing
