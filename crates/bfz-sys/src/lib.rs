@@ -227,6 +227,39 @@ pub struct bfz_debug_report {
     pub kind_count: [[u32; BFZ_NUM_CHIPS]; BFZ_NUM_KINDS],
 }
 
+pub const BFZ_LOOKUP_MAX_VALUES: usize = 7;
+/// One lookup key whose sends and receives differ (lookup/debug.rs:160-171): Montgomery values,
+/// `field_to_int` nets (lookup/debug.rs:46-54), and the first interaction that carries the key.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct bfz_lookup_discrepancy {
+    pub kind: i32,
+    pub nvals: i32,
+    pub values: [u32; BFZ_LOOKUP_MAX_VALUES],
+    pub net: i32,
+    pub chip_net: [i32; BFZ_NUM_CHIPS],
+    pub chip_count: [u32; BFZ_NUM_CHIPS],
+    pub first_chip: i32,
+    pub first_interaction: i32,
+    pub first_row: i64,
+}
+/// `debug_interactions_with_all_chips` (lookup/debug.rs:125-196) as plain data; `balanced` is its
+/// return value.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct bfz_lookup_report {
+    pub balanced: i32,
+    pub total_net: i32,
+    pub interactions: u64,
+    pub distinct_keys: u64,
+    pub unbalanced_keys: u64,
+    pub chip_distinct: [u64; BFZ_NUM_CHIPS],
+    pub n_written: u32,
+    pub rounds: u32,
+    pub tag_collisions: u32,
+    pub table_bytes: u64,
+}
+
 /// One proof's verdict from `bfz_verify_batch` (`StarkMachine::verify`, machine.rs:258-284):
 /// `why` is a NUL-terminated reason, empty when `ok == 1`.
 #[repr(C)]
@@ -273,6 +306,15 @@ extern "C" {
                                         widths: *const usize, nchips: usize,
                                         ch: *mut bfz_challenger, flags: c_uint,
                                         out: *mut bfz_debug_report) -> c_int;
+    pub fn bfz_record_debug_interactions(pk: *const bfz_pk, rec: *const bfz_record,
+                                         kinds_mask: c_uint, report: *mut bfz_lookup_report,
+                                         out: *mut bfz_lookup_discrepancy, cap: usize) -> c_int;
+    pub fn bfz_debug_interactions_traces(pk: *const bfz_pk, chips: *const c_int,
+                                         traces: *const *const u32, heights: *const usize,
+                                         widths: *const usize, nchips: usize, kinds_mask: c_uint,
+                                         on_device: c_int, report: *mut bfz_lookup_report,
+                                         out: *mut bfz_lookup_discrepancy, cap: usize) -> c_int;
+    pub fn bfz_setup_host(elf: *const c_char, pk: *mut *mut bfz_pk) -> c_int;
     pub fn bfz_trace_device(elf: *const c_char, stdin_data: *const u8, nin: usize, chip: c_int,
                             out: *mut *mut u32, height: *mut usize, width: *mut usize) -> c_int;
 

@@ -426,8 +426,9 @@ int bfz_commit_fri_sharded(const uint32_t* d_cols, int log_n, size_t w_local, in
 
 /* ---- Constraint checker: the reference's `--features debug` mode, on the device ----
  * Replaces debug_constraints (crates/stark/src/debug.rs:24-105), StarkMachine::debug_constraints
- * (crates/stark/src/machine.rs:288-387) and the interaction balance of
- * debug_interactions_with_all_chips (crates/stark/src/lookup/debug.rs:59-196).
+ * (crates/stark/src/machine.rs:288-387) and the per-kind interaction balance of
+ * debug_interactions_with_all_chips (crates/stark/src/lookup/debug.rs:59-196); its per-key
+ * result is bfz_record_debug_interactions / bfz_debug_interactions_traces further down.
  *
  * Every row i of a chip's trace is checked against Chip::eval (chip.rs:222-228) with row
  * (i + 1) mod height as the next row, is_first = [i == 0], is_last = [i == height - 1] and
@@ -495,6 +496,66 @@ int bfz_debug_constraints_traces(const bfz_pk* pk, const int* chips, const uint3
                                  const size_t* heights, const size_t* widths, size_t nchips,
                                  bfz_challenger* ch, unsigned flags, bfz_debug_report* out);
 
+/* ---- Per-key lookup discrepancies: the rest of debug_interactions_with_all_chips ----
+ * Which call covers which part of crates/stark/src/lookup/debug.rs: the kind_* table of
+ * bfz_debug_report above is the per-KIND balance under the LogUp challenges (what tells that
+ * "Byte is off by -1"); the calls below are the per-KEY result the reference prints
+ * (lookup/debug.rs:59-196): for every lookup tuple "{kind} (v0, v1, ...)" (:100) with a non-zero
+ * multiplicity (:94) the sends minus the receives over all chips (:109-114,148-149), each chip's
+ * share of it (:151), the chips' distinct-key counts (:153) and the verdict (:175-195).  The
+ * multiset does not depend on alpha or beta, so it also shows keys that differ while the totals
+ * match (:188-191).
+ *
+ * Records come in ascending order of (kind, then the values' canonical integers,
+ * lexicographically).  This is deliberately NOT the reference's order, which sorts the keys as
+ * strings (BTreeMap<String, ..>, where "10" comes before "9").  Field words are Montgomery form.
+ * Every interaction is counted once: for each record the sum of chip_net is congruent to net
+ * mod p. */
+#define BFZ_LOOKUP_MAX_VALUES 7
+typedef struct {
+  int32_t kind;  /* LookupKind 1..7 */
+  int32_t nvals;
+  uint32_t values[BFZ_LOOKUP_MAX_VALUES]; /* Montgomery; unused entries 0 */
+  int32_t net;                       /* field_to_int(sends - receives) over all chips, != 0 */
+  int32_t chip_net[BFZ_NUM_CHIPS];   /* field_to_int per chip index (lookup/debug.rs:151) */
+  uint32_t chip_count[BFZ_NUM_CHIPS]; /* non-zero-multiplicity interactions with this key */
+  int32_t first_chip;                /* witness: the smallest (chip, row, interaction) */
+  int32_t first_interaction;         /* index in sends-then-receives chain order (lookup/debug.rs:80) */
+  int64_t first_row;                 /* natural row order */
+} bfz_lookup_discrepancy;
+typedef struct {
+  int32_t balanced;         /* the reference's return value: 1 = no key with a non-zero net */
+  int32_t total_net;        /* field_to_int of the sum over all keys (lookup/debug.rs:150,180) */
+  uint64_t interactions;    /* non-zero-multiplicity interactions of the selected kinds */
+  uint64_t distinct_keys;
+  uint64_t unbalanced_keys; /* may exceed cap */
+  uint64_t chip_distinct[BFZ_NUM_CHIPS]; /* "{} chip has {} distinct events" (lookup/debug.rs:153) */
+  uint32_t n_written;       /* min(unbalanced_keys, cap) */
+  uint32_t rounds, tag_collisions; /* diagnostics of the device path, 0 on the host path */
+  uint64_t table_bytes;            /* device memory of the aggregation, 0 on the host path */
+} bfz_lookup_report;
+
+/* debug_interactions_with_all_chips on a device record (traces generated on the device as
+ * bfz_record_prove does).  kinds_mask: bit k selects LookupKind k (the reference's
+ * interaction_kinds); 0 or a bit outside 1..7 is an error.  out receives the first
+ * min(unbalanced_keys, cap) records (cap > 0 needs out).  Returns 0 whenever the check ran; a
+ * negative status is a real error: bad shapes, a bad mask, a device error, or not enough device
+ * memory for the aggregation (the message names the bytes needed). */
+int bfz_record_debug_interactions(const bfz_pk* pk, const bfz_record* rec, unsigned kinds_mask,
+                                  bfz_lookup_report* report, bfz_lookup_discrepancy* out,
+                                  size_t cap);
+/* The same from host main traces (arguments and validation of bfz_debug_constraints_traces,
+ * preprocessed traces from the key, machine.rs:309-312).  on_device = 0 runs the host path: the
+ * same Lookup tables single-threaded over an ordered map, no device needed. */
+int bfz_debug_interactions_traces(const bfz_pk* pk, const int* chips, const uint32_t* const* traces,
+                                  const size_t* heights, const size_t* widths, size_t nchips,
+                                  unsigned kinds_mask, int on_device, bfz_lookup_report* report,
+                                  bfz_lookup_discrepancy* out, size_t cap);
+/* A key that holds the program only (no preprocessed commit, no device data), for the host paths:
+ * bfz_debug_interactions_traces with on_device = 0 accepts it on a machine without a GPU.  Every
+ * call that needs the device key refuses it with an error. */
+int bfz_setup_host(const char* elf, bfz_pk** pk);
+
 /* FRI_QUERIES (kb31_poseidon2.rs:59-62): 1..4096, or 0 = environment FRI_QUERIES / 84. */
 int bfz_set_num_queries(int num_queries);
 
@@ -510,7 +571,9 @@ int bfz_set_pcs_variant(int observe_openings);
  * on_device = 1 run its host side only (stages, packing, the queries the packing keeps on the
  * host) with a stand-in for the kernels that reports no failure and needs no device, so that side
  * is testable without a GPU (tests/test_verify_batch.py); its verdicts are then not a
- * verification.  0 (default) = off. */
+ * verification.  Bit 2 cuts the key hash of the device path of bfz_*_debug_interactions to its low
+ * 12 bits before anything uses it (home slot and tag alike), so distinct keys share tags and the
+ * multi-round path runs; verdicts and records must not change.  0 (default) = off. */
 int bfz_set_fault_injection(int mask);
 
 /* Proof wire format.  bfz_prove* return the BFZ1 normal form; bfz_proof_to_bincode turns it

@@ -71,6 +71,25 @@ class DebugReportC(ctypes.Structure):
                 ("kind_count", (c_uint32 * NUM_CHIPS) * NUM_KINDS)]
 
 
+LOOKUP_MAX_VALUES = 7  # BFZ_LOOKUP_MAX_VALUES
+
+
+class LookupDiscrepancyC(ctypes.Structure):
+    """bfz_lookup_discrepancy: one lookup key whose sends and receives differ."""
+    _fields_ = [("kind", c_int32), ("nvals", c_int32), ("values", c_uint32 * LOOKUP_MAX_VALUES),
+                ("net", c_int32), ("chip_net", c_int32 * NUM_CHIPS),
+                ("chip_count", c_uint32 * NUM_CHIPS), ("first_chip", c_int32),
+                ("first_interaction", c_int32), ("first_row", c_int64)]
+
+
+class LookupReportC(ctypes.Structure):
+    """bfz_lookup_report: debug_interactions_with_all_chips' outcome as plain data."""
+    _fields_ = [("balanced", c_int32), ("total_net", c_int32), ("interactions", c_uint64),
+                ("distinct_keys", c_uint64), ("unbalanced_keys", c_uint64),
+                ("chip_distinct", c_uint64 * NUM_CHIPS), ("n_written", c_uint32),
+                ("rounds", c_uint32), ("tag_collisions", c_uint32), ("table_bytes", c_uint64)]
+
+
 class VerifyOutcomeC(ctypes.Structure):
     """bfz_verify_outcome: one proof's verdict from bfz_verify_batch."""
     _fields_ = [("ok", c_int32), ("query", c_int32), ("why", ctypes.c_char * 120)]
@@ -119,6 +138,13 @@ SIGNATURES = [
     ("bfz_debug_constraints_traces", c_int, [c_void_p, POINTER(c_int), POINTER(POINTER(c_uint32)),
                                              POINTER(c_size_t), POINTER(c_size_t), c_size_t,
                                              POINTER(Challenger), c_uint, POINTER(DebugReportC)]),
+    ("bfz_record_debug_interactions", c_int, [c_void_p, c_void_p, c_uint, POINTER(LookupReportC),
+                                              POINTER(LookupDiscrepancyC), c_size_t]),
+    ("bfz_debug_interactions_traces", c_int, [c_void_p, POINTER(c_int), POINTER(POINTER(c_uint32)),
+                                              POINTER(c_size_t), POINTER(c_size_t), c_size_t,
+                                              c_uint, c_int, POINTER(LookupReportC),
+                                              POINTER(LookupDiscrepancyC), c_size_t]),
+    ("bfz_setup_host", c_int, [c_char_p, POINTER(c_void_p)]),
     ("bfz_trace_device", c_int, [c_char_p, POINTER(c_uint8), c_size_t, c_int,
                                  POINTER(POINTER(c_uint32)), POINTER(c_size_t), POINTER(c_size_t)]),
     ("bfz_setup", c_int, [c_char_p, POINTER(c_void_p), POINTER(c_uint32)]),
@@ -246,5 +272,5 @@ def take_bytes(ptr, n: int) -> bytes:
 
 
 __all__ = ["lib", "check", "init", "u8buf", "take_bytes", "BfzError", "Timings", "Events", "LIB_PATH",
-           "ChipCheck", "DebugReportC", "VerifyOutcomeC",
+           "ChipCheck", "DebugReportC", "VerifyOutcomeC", "LookupDiscrepancyC", "LookupReportC",
            "SIGNATURES", "byref"]

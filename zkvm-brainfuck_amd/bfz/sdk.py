@@ -22,6 +22,9 @@ and of the reference's debug mode (crates/stark/src/machine.rs:288-387, debug.rs
     report = client.debug_constraints(pk, stdin) # StarkMachine::debug_constraints on the device
     report = prover.debug_constraints(pk, traces)
     print(report)                                # chip, row and constraint of the first failure
+    lookups = client.debug_interactions(pk, stdin)   # debug_interactions_with_all_chips
+    lookups = prover.debug_interactions(pk, traces)  # (lookup/debug.rs:125-196): per-key
+    print(lookups)                                   # send-receive discrepancies
 
 Errors raise (the reference returns Err / panics in the same places).  Proving runs on the GPU
 through libbfz; verification runs the host verifier compiled into the same library.
@@ -649,6 +652,155 @@ def _debug_constraints_record(self, pk: BfProvingKey, stdin, ch: Optional[Challe
 
 CoreProver.debug_constraints = _debug_constraints_traces
 ProverClient.debug_constraints = _debug_constraints_record
+
+
+# ---- per-key lookup discrepancies (crates/stark/src/lookup/debug.rs:59-196)
+_RINV = pow(1 << 32, -1, _P)  # Montgomery word -> canonical integer
+
+
+@dataclass
+class LookupDiscrepancy:
+    """bfz_lookup_discrepancy: a lookup key whose sends and receives differ.  values are
+    canonical integers; net, chip_net are field_to_int values (lookup/debug.rs:46-54);
+    first_* is the smallest (chip, row, interaction) that carries the key."""
+    kind: int
+    values: List[int]
+    net: int
+    chip_net: List[int]
+    chip_count: List[int]
+    first_chip: int
+    first_row: int
+    first_interaction: int
+
+    @property
+    def key(self) -> str:
+        """The reference's key string (lookup/debug.rs:100)."""
+        return f"{KINDS[self.kind]} ({', '.join(str(v) for v in self.values)})"
+
+    def lines(self) -> List[str]:
+        out = [f"Lookup key: {self.key} Send-Receive Discrepancy: {self.net}"]
+        for c in sorted((c for c in range(len(CHIPS)) if self.chip_count[c]), key=lambda c: CHIPS[c]):
+            out.append(f" {CHIPS[c]} chip's send-receive discrepancy for this key is {self.chip_net[c]}")
+        out.append(f" first seen at {CHIPS[self.first_chip]} row {self.first_row} "
+                   f"interaction {self.first_interaction}")
+        return out
+
+
+@dataclass
+class LookupReport:
+    """bfz_lookup_report and its records: what debug_interactions_with_all_chips
+    (lookup/debug.rs:125-196) prints and returns.  discrepancies holds the first `limit` unbalanced
+    keys in (kind, values) order; unbalanced_keys counts all of them.  str(report) gives the
+    reference's lines (keys in our order, not its string order) plus a witness line per key."""
+    balanced: bool
+    total_net: int
+    interactions: int
+    distinct_keys: int
+    unbalanced_keys: int
+    chip_distinct: List[int]
+    discrepancies: List[LookupDiscrepancy]
+    rounds: int = 0
+    tag_collisions: int = 0
+    table_bytes: int = 0
+    chips: Optional[List[int]] = None  # included chips, when the caller knows them
+
+    def __str__(self) -> str:
+        inc = self.chips if self.chips is not None else [
+            c for c in range(len(CHIPS)) if self.chip_distinct[c]]
+        lines = [f"{CHIPS[c]} chip has {self.chip_distinct[c]} distinct events" for c in inc]
+        lines += ["Final counts below.", "=================="]
+        for d in self.discrepancies:
+            lines += d.lines()
+        if self.unbalanced_keys > len(self.discrepancies):
+            lines.append(f"... {self.unbalanced_keys - len(self.discrepancies)} more unbalanced keys")
+        lines.append("==================")
+        if self.balanced:
+            lines.append("All chips have the same number of sends and receives.")
+        else:
+            lines += ["Positive values mean sent more than received.",
+                      "Negative values mean received more than sent."]
+            if self.total_net != 0:
+                lines.append(f"Total send-receive discrepancy: {self.total_net}")
+                lines.append("you're sending more than you are receiving" if self.total_net > 0
+                             else "you're receiving more than you are sending")
+            else:
+                lines += ["the total number of sends and receives match, but the keys don't match",
+                          "check the arguments"]
+        return "\n".join(lines)
+
+
+def kinds_mask(kinds=None) -> int:
+    """bit k per selected LookupKind: None = all, else kind indices or names of KINDS."""
+    if kinds is None:
+        return 0xFE
+    m = 0
+    for k in kinds:
+        m |= 1 << (KINDS.index(k) if isinstance(k, str) else int(k))
+    return m
+
+
+def _lookup_report(rep, recs, chips=None) -> LookupReport:
+    ds = []
+    for i in range(rep.n_written):
+        r = recs[i]
+        ds.append(LookupDiscrepancy(
+            kind=r.kind, values=[r.values[v] * _RINV % _P for v in range(r.nvals)], net=r.net,
+            chip_net=list(r.chip_net), chip_count=list(r.chip_count), first_chip=r.first_chip,
+            first_row=r.first_row, first_interaction=r.first_interaction))
+    return LookupReport(
+        balanced=bool(rep.balanced), total_net=rep.total_net, interactions=rep.interactions,
+        distinct_keys=rep.distinct_keys, unbalanced_keys=rep.unbalanced_keys,
+        chip_distinct=list(rep.chip_distinct), discrepancies=ds, rounds=rep.rounds,
+        tag_collisions=rep.tag_collisions, table_bytes=rep.table_bytes, chips=chips)
+
+
+def host_key(elf: str) -> BfProvingKey:
+    """bfz_setup_host: a key that holds the program only, for the host paths
+    (debug_interactions(..., on_device=False)) on a machine without a GPU."""
+    h = ctypes.c_void_p()
+    check(lib().bfz_setup_host(elf.encode(), ctypes.byref(h)))
+    return BfProvingKey(handle=h.value, elf=elf, vk=BfVerifyingKey(commit=[], elf=elf))
+
+
+def _debug_interactions_traces(self, pk: BfProvingKey, traces, kinds=None, limit: int = 256,
+                               on_device: bool = True) -> LookupReport:
+    """debug_interactions_with_all_chips (lookup/debug.rs:125-196) from host main traces
+    (bfz_debug_interactions_traces).  on_device=False runs the host path (no GPU needed; pk may
+    be a host_key)."""
+    if on_device:
+        init()
+    mats, chips, ptrs, hs, ws, k = _trace_args(traces)
+    rep = _lib.LookupReportC()
+    recs = (_lib.LookupDiscrepancyC * max(1, int(limit)))()
+    check(lib().bfz_debug_interactions_traces(
+        ctypes.c_void_p(pk.handle), chips, ptrs, hs, ws, k, kinds_mask(kinds), int(bool(on_device)),
+        ctypes.byref(rep), recs, int(limit)))
+    return _lookup_report(rep, recs, sorted(c for c, _, _ in traces))
+
+
+def _debug_interactions_record(self, pk: BfProvingKey, stdin, kinds=None,
+                               limit: int = 256) -> LookupReport:
+    """debug_interactions_with_all_chips (lookup/debug.rs:125-196) of (pk's program, stdin) on the
+    device: bfz_record_new, then bfz_record_debug_interactions aggregates the traces the GPU
+    proves from."""
+    init(self.device)
+    buf, n = u8buf(bytes(stdin))
+    rec = ctypes.c_void_p()
+    cyc = ctypes.c_uint64()
+    check(lib().bfz_record_new(ctypes.c_void_p(pk.handle), buf, n, ctypes.byref(rec),
+                               ctypes.byref(cyc)))
+    try:
+        rep = _lib.LookupReportC()
+        recs = (_lib.LookupDiscrepancyC * max(1, int(limit)))()
+        check(lib().bfz_record_debug_interactions(ctypes.c_void_p(pk.handle), rec, kinds_mask(kinds),
+                                                  ctypes.byref(rep), recs, int(limit)))
+    finally:
+        lib().bfz_record_free(rec)
+    return _lookup_report(rep, recs)
+
+
+CoreProver.debug_interactions = _debug_interactions_traces
+ProverClient.debug_interactions = _debug_interactions_record
 
 
 def set_num_queries(q: int) -> None:

@@ -18,6 +18,7 @@
 #include "debug_check.h"
 #include "fri.h"
 #include "logup.h"
+#include "lookup_debug.h"
 #include "merkle.h"
 #include "ntt.h"
 #include "pcs_sharded.h"
@@ -30,6 +31,7 @@
 
 struct bfz_pk {
   std::shared_ptr<const bfz::ProvingKey> pk;  // shared with the per-program setup cache
+  bool host_only = false;                     // bfz_setup_host: the program alone, no device data
 };
 struct bfz_main_data {
   std::shared_ptr<const bfz::ProvingKey> pk;  // the key the commit was made for
@@ -66,6 +68,13 @@ int g_num_queries = -1;
 int g_observe_openings = -1;  // -1: BFZ_OBSERVE_OPENINGS / default
 int g_fault = 0;              // bfz_set_fault_injection (tests only)
 int g_bound = -1;             // the device bfz_init bound this process to
+
+// The device key of a handle; a bfz_setup_host key has none.
+const bfz::ProvingKey& dkey(const bfz_pk* pk) {
+  if (pk->host_only)
+    throw std::runtime_error("this key was made by bfz_setup_host: it holds no device data");
+  return *pk->pk;
+}
 
 int fail(const std::exception& e, int code = -1) {
   g_err = e.what();
@@ -593,6 +602,20 @@ int bfz_setup(const char* elf, bfz_pk** pk, uint32_t vk_commit[8]) {
   });
 }
 
+int bfz_setup_host(const char* elf, bfz_pk** pk) {
+  return guarded([&] {
+    if (!elf || !pk) throw std::runtime_error("null argument");
+    auto key = std::make_unique<bfz::ProvingKey>();
+    key->program = bfz::Program::parse(elf);
+    key->idx_of_chip.fill(-1);
+    auto k = std::make_unique<bfz_pk>();
+    k->pk = std::move(key);
+    k->host_only = true;
+    *pk = k.release();
+    return 0;
+  });
+}
+
 void bfz_pk_free(bfz_pk* pk) {
   std::lock_guard<std::mutex> lk(g_mu);
   delete pk;
@@ -658,13 +681,13 @@ int bfz_pk_from_host(const int* chips, const uint32_t* const* traces, const size
 int bfz_pk_commit(const bfz_pk* pk, uint32_t commit[8]) {
   return guarded([&] {
     if (!pk || !commit) throw std::runtime_error("null argument");
-    std::memcpy(commit, pk->pk->prep.tree.root, 32);
+    std::memcpy(commit, dkey(pk).prep.tree.root, 32);
     return 0;
   });
 }
 
 int bfz_prove(const bfz_pk* pk, const uint8_t* in, size_t nin, uint8_t** proof, size_t* len) {
-  return guarded([&] { return emit(bfz::prove(*pk->pk, in, nin, opts(), nullptr), proof, len); });
+  return guarded([&] { return emit(bfz::prove(dkey(pk), in, nin, opts(), nullptr), proof, len); });
 }
 
 int bfz_synchronize(void) {
@@ -680,7 +703,7 @@ int bfz_prove_traces(const bfz_pk* pk, const int* chips, const uint32_t* const* 
   return guarded([&] {
     bfz::DeviceTraces dt;
     bfz::upload_host_traces(chips, traces, heights, widths, nchips, dt, bfz::stream());
-    return emit(bfz::prove_device(*pk->pk, dt, opts(), nullptr), proof, len);
+    return emit(bfz::prove_device(dkey(pk), dt, opts(), nullptr), proof, len);
   });
 }
 
@@ -719,7 +742,7 @@ int bfz_challenger_observe_pk(const bfz_pk* pk, bfz_challenger* ch) {
   return guarded([&] {
     if (!pk || !ch) throw std::runtime_error("null argument");
     bfz::Challenger c = from_c(ch);
-    c.observe_digest(pk->pk->prep.tree.root);  // observe_into (prover.rs:595-601)
+    c.observe_digest(dkey(pk).prep.tree.root);  // observe_into (prover.rs:595-601)
     for (int i = 0; i < 7; i++) c.observe(0);
     to_c(c, ch);
     return 0;
@@ -762,7 +785,7 @@ int bfz_open(const bfz_pk* pk, bfz_main_data* data, bfz_challenger* ch, uint8_t*
     if (data->pk && data->pk != pk->pk)
       throw std::runtime_error("open: main data was committed for another key");
     bfz::Challenger after;
-    emit(bfz::open_main(*pk->pk, data->md, from_c(ch), opts(), &after), proof, len);
+    emit(bfz::open_main(dkey(pk), data->md, from_c(ch), opts(), &after), proof, len);
     to_c(after, ch);  // MachineProver::open advances its &mut challenger
     return 0;
   });
@@ -799,7 +822,7 @@ int bfz_prove_batch(const bfz_pk* pk, const uint8_t* const* stdins, const size_t
                                  std::to_string(bfz::MAX_LANES) + ", got '" + e + "'");
       return (int)v;
     }();
-    auto v = bfz::prove_batch(*pk->pk, jobs, opts(), E, inflight, &bs);
+    auto v = bfz::prove_batch(dkey(pk), jobs, opts(), E, inflight, &bs);
     emit_all(v, proofs, proof_lens, (size_t)-1);
     if (stats) {
       stats->wall_ms = bs.wall_ms;
@@ -1218,7 +1241,7 @@ int bfz_record_prove(const bfz_pk* pk, const bfz_record* rec, uint8_t** proof, s
     bfz::ProveOptions o = opts();
     o.timing = t != nullptr;
     bfz::StageTimes st;
-    auto v = bfz::prove_events(*pk->pk, rec->ev, o, &st);
+    auto v = bfz::prove_events(dkey(pk), rec->ev, o, &st);
     fill_timings(st, t);
     const int r = emit(std::move(v), proof, len);
     bfz::host_mark("emitted");
@@ -1234,7 +1257,7 @@ int bfz_record_debug_constraints(const bfz_pk* pk, const bfz_record* rec, bfz_ch
     bfz::DeviceTraces dt;
     bfz::generate_traces_device(rec->ev, dt, bfz::stream());
     bfz::DebugReport r;
-    bfz::debug_constraints_device(*pk->pk, dt, c, (flags & 1) != 0, r);
+    bfz::debug_constraints_device(dkey(pk), dt, c, (flags & 1) != 0, r);
     to_c(r, out);
     to_c(c, ch);  // debug_constraints samples from its &mut challenger (machine.rs:300-303)
     return 0;
@@ -1251,9 +1274,91 @@ int bfz_debug_constraints_traces(const bfz_pk* pk, const int* chips, const uint3
     bfz::DeviceTraces dt;
     bfz::upload_host_traces(chips, traces, heights, widths, nchips, dt, bfz::stream());
     bfz::DebugReport r;
-    bfz::debug_constraints_device(*pk->pk, dt, c, (flags & 1) != 0, r);
+    bfz::debug_constraints_device(dkey(pk), dt, c, (flags & 1) != 0, r);
     to_c(r, out);
     to_c(c, ch);
+    return 0;
+  });
+}
+
+}  // extern "C"
+namespace {
+void to_c(const bfz::LookupReport& r, bfz_lookup_report* o, bfz_lookup_discrepancy* out) {
+  static_assert(sizeof(bfz_lookup_discrepancy) == 120 && sizeof(bfz_lookup_report) == 120,
+                "bfz_lookup_* layouts");
+  static_assert(BFZ_LOOKUP_MAX_VALUES == bfz::LK_MAX_VALUES, "bfz.h sizes");
+  std::memset(o, 0, sizeof *o);
+  o->balanced = r.balanced;
+  o->total_net = r.total_net;
+  o->interactions = r.interactions;
+  o->distinct_keys = r.distinct_keys;
+  o->unbalanced_keys = r.unbalanced_keys;
+  for (int c = 0; c < bfz::NUM_CHIPS; c++) o->chip_distinct[c] = r.chip_distinct[c];
+  o->n_written = (uint32_t)r.recs.size();
+  o->rounds = r.rounds;
+  o->tag_collisions = r.tag_collisions;
+  o->table_bytes = r.table_bytes;
+  for (size_t k = 0; k < r.recs.size(); k++) {
+    const bfz::LookupDiscrepancy& d = r.recs[k];
+    bfz_lookup_discrepancy& q = out[k];
+    std::memset(&q, 0, sizeof q);
+    q.kind = d.kind;
+    q.nvals = d.nvals;
+    for (int v = 0; v < d.nvals; v++) q.values[v] = kb::to_mont(d.values[v]);
+    q.net = d.net;
+    for (int c = 0; c < bfz::NUM_CHIPS; c++) {
+      q.chip_net[c] = d.chip_net[c];
+      q.chip_count[c] = d.chip_count[c];
+    }
+    q.first_chip = d.first_chip;
+    q.first_interaction = d.first_interaction;
+    q.first_row = d.first_row;
+  }
+}
+void check_lookup_args(const bfz_pk* pk, unsigned kinds_mask, const bfz_lookup_report* report,
+                       const bfz_lookup_discrepancy* out, size_t cap) {
+  if (!pk || !report) throw std::runtime_error("null argument");
+  if (cap > 0 && !out) throw std::runtime_error("debug_interactions: cap > 0 needs an output array");
+  if (cap > 0xFFFFFFF0u) throw std::runtime_error("debug_interactions: cap too large");
+  bfz::check_kinds_mask(kinds_mask);
+}
+}  // namespace
+extern "C" {
+
+int bfz_record_debug_interactions(const bfz_pk* pk, const bfz_record* rec, unsigned kinds_mask,
+                                  bfz_lookup_report* report, bfz_lookup_discrepancy* out,
+                                  size_t cap) {
+  return guarded([&] {
+    check_lookup_args(pk, kinds_mask, report, out, cap);
+    if (!rec) throw std::runtime_error("null argument");
+    bfz::LookupReport r;
+    {
+      bfz::DeviceTraces dt;
+      bfz::generate_traces_device(rec->ev, dt, bfz::stream());
+      bfz::debug_interactions_device(dkey(pk), dt, kinds_mask, cap, (g_fault & 4) != 0, r);
+    }
+    to_c(r, report, out);
+    return 0;
+  });
+}
+
+int bfz_debug_interactions_traces(const bfz_pk* pk, const int* chips, const uint32_t* const* traces,
+                                  const size_t* heights, const size_t* widths, size_t nchips,
+                                  unsigned kinds_mask, int on_device, bfz_lookup_report* report,
+                                  bfz_lookup_discrepancy* out, size_t cap) {
+  return guarded([&] {
+    check_lookup_args(pk, kinds_mask, report, out, cap);
+    if (!chips || !traces || !heights || !widths) throw std::runtime_error("null argument");
+    bfz::LookupReport r;
+    if (!on_device) {
+      bfz::debug_interactions_host(pk->pk->program, chips, traces, heights, widths, nchips,
+                                   kinds_mask, cap, r);
+    } else {
+      bfz::DeviceTraces dt;
+      bfz::upload_host_traces(chips, traces, heights, widths, nchips, dt, bfz::stream());
+      bfz::debug_interactions_device(dkey(pk), dt, kinds_mask, cap, (g_fault & 4) != 0, r);
+    }
+    to_c(r, report, out);
     return 0;
   });
 }
@@ -1277,7 +1382,7 @@ int bfz_record_prove_repeat(const bfz_pk* pk, const bfz_record* rec, int count, 
       for (int k; !failed.load(std::memory_order_relaxed) && (k = next.fetch_add(1)) < count;) {
         std::vector<uint8_t> v;
         try {
-          v = bfz::prove_events(*pk->pk, rec->ev, o, nullptr);
+          v = bfz::prove_events(dkey(pk), rec->ev, o, nullptr);
         } catch (...) {
           failed.store(true, std::memory_order_relaxed);
           throw;
@@ -1319,7 +1424,7 @@ int bfz_record_prove_sharded(const bfz_pk* pk, const bfz_record* rec, int rank, 
     bfz::ProveOptions o = opts();
     o.timing = t != nullptr;
     bfz::StageTimes st;
-    auto v = bfz::prove_events(*pk->pk, rec->ev, o, &st);
+    auto v = bfz::prove_events(dkey(pk), rec->ev, o, &st);
     fill_timings(st, t);
     return emit(std::move(v), proof, len);
   });
@@ -1385,7 +1490,7 @@ int bfz_record_prove_shard_solo(const bfz_pk* pk, const bfz_record* rec, int ran
     bfz::ProveOptions o = opts();
     o.timing = t != nullptr;  // t == nullptr: no stage events or kernel probes (wall-clock runs)
     bfz::StageTimes st;
-    (void)bfz::prove_events(*pk->pk, rec->ev, o, t ? &st : nullptr);  // not a proof: discarded
+    (void)bfz::prove_events(dkey(pk), rec->ev, o, t ? &st : nullptr);  // not a proof: discarded
     if (t) fill_timings(st, t);
     auto& olog = solo_overlap_log();  // the proof's events have resolved into the slots
     olog.assign(ov.size(), 0.0);
@@ -1441,7 +1546,9 @@ int bfz_set_pcs_variant(int observe_openings) {
 
 int bfz_set_fault_injection(int mask) {
   return guarded([&] {
-    if (mask & ~3) throw std::runtime_error("fault mask: bits 0 (device challenger) and 1 (verifier kernels stand-in) only");
+    if (mask & ~7)
+      throw std::runtime_error("fault mask: bits 0 (device challenger), 1 (verifier kernels stand-in) and "
+                               "2 (debug_interactions 12-bit key hash) only");
     g_fault = mask;
     return 0;
   });

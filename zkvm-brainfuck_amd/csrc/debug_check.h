@@ -1,7 +1,11 @@
 // Constraint checker: the reference's `--features debug` mode on the device.
 //   debug_constraints                      crates/stark/src/debug.rs:24-105
 //   StarkMachine::debug_constraints        crates/stark/src/machine.rs:288-387
-//   debug_interactions_with_all_chips      crates/stark/src/lookup/debug.rs:59-196
+//   debug_interactions_with_all_chips      crates/stark/src/lookup/debug.rs:59-196, in part:
+//     here (bfz_record_debug_constraints): the balance per LookupKIND and chip under the LogUp
+//     challenges, kind_sum / kind_net / kind_count;
+//     lookup_debug.h (bfz_record_debug_interactions): the per-KEY result the reference prints,
+//     every tuple's sends minus receives and each chip's share (debug.rs:100-115,145-171).
 // The AIRs and the LogUp constraints are the templates of air.h, evaluated on the TRACE domain
 // with a third accumulator (FirstFailAcc) instead of the quotient's alpha fold: row i is local,
 // row (i + 1) mod h is next, is_first = [i == 0], is_last = [i == h - 1], is_transition =
