@@ -386,6 +386,16 @@ extern "C" {
                                   ctx: *mut c_void, out: *mut u32, cap: usize,
                                   nwords: *mut usize) -> c_int;
 
+    /// `utils::uni_stark_prove` / `uni_stark_verify` (crates/core/machine/src/utils/prove.rs:97-159)
+    /// of one chip's AIR over one trace: Cpu 0, AddSub 2, Jump 3, MemoryInstrs 6, IO 7.
+    pub fn bfz_uni_info(chip: c_int, num_constraints: *mut c_int, degree: *mut c_int,
+                        log_quotient_degree: *mut c_int) -> c_int;
+    pub fn bfz_uni_prove(chip: c_int, trace: *const u32, height: usize, width: usize,
+                         ch: *mut bfz_challenger, proof: *mut *mut u8, proof_len: *mut usize,
+                         timings: *mut bfz_timings) -> c_int;
+    pub fn bfz_uni_verify(chip: c_int, ch: *mut bfz_challenger, proof: *const u8, proof_len: usize,
+                          out: *mut bfz_verify_outcome) -> c_int;
+
     pub fn bfz_set_num_queries(num_queries: c_int) -> c_int;
     pub fn bfz_set_pcs_variant(observe_openings: c_int) -> c_int;
     /// Test-only fault injection (bit 0: perturb the device challenger); 0 = off.

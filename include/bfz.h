@@ -21,6 +21,10 @@
  *   bfz_coset_lde    Radix2DitParallel::coset_lde_batch + bit_reverse_rows (inside
  *                    TwoAdicFriPcs::commit, called at prover.rs:227,334,411)
  *   bfz_poseidon2_permute  Poseidon2KoalaBear<16> (kb31_poseidon2.rs:35-50)
+ *   bfz_uni_prove    utils::uni_stark_prove -> p3_uni_stark::prove
+ *                                                         crates/core/machine/src/utils/prove.rs:97-127
+ *   bfz_uni_verify   utils::uni_stark_verify -> p3_uni_stark::verify
+ *                                                         crates/core/machine/src/utils/prove.rs:129-159
  *
  * Conventions: field elements are uint32_t in MONTGOMERY form (x * 2^32 mod p), i.e.
  * byte-identical to a Rust `[KoalaBear]` slice; matrices are row-major.  Every function
@@ -555,6 +559,43 @@ int bfz_debug_interactions_traces(const bfz_pk* pk, const int* chips, const uint
  * bfz_debug_interactions_traces with on_device = 0 accepts it on a machine without a GPU.  Every
  * call that needs the device key refuses it with an error. */
 int bfz_setup_host(const char* elf, bfz_pk** pk);
+
+/* ---- Per-chip uni-STARK proofs: utils::uni_stark_prove / uni_stark_verify ----
+ * Replaces bf_core_machine::utils::{uni_stark_prove, uni_stark_verify}
+ * (crates/core/machine/src/utils/prove.rs:97-159): p3_uni_stark::{prove, verify} of ONE chip's
+ * AIR over one trace, with the machine prover's PCS and challenger, no public values
+ * (utils/prove.rs:111), no LogUp and no other chip -- what the reference's chip tests run
+ * (alu/mod.rs:221-245 AddSub, jump/mod.rs:34-52 Jump, memory/instructions/mod.rs:21-37
+ * MemoryInstrs).  Under the uni-STARK builders a chip's send / receive are no-ops
+ * (air/builder.rs:232-239,273-275), so exactly the chip's AIR constraints are proven.
+ *
+ * chip is one of Cpu 0, AddSub 2, Jump 3, MemoryInstrs 6, IO 7.  Program 1, Memory 4 and Byte 5
+ * have no AIR constraints of their own or need a preprocessed trace, which p3_uni_stark does not
+ * take: every call refuses them with a negative status.
+ *
+ *   bfz_uni_info    host only: the constraints the chip's AIR emits, their maximal degree and
+ *                   log_quotient_degree = log2_ceil(degree - 1) (crates/stark/src/chip.rs:82-87,
+ *                   without its floor of 3 for chips with interactions: there are none here),
+ *                   all computed from the AIR itself.  Any output pointer may be NULL.
+ *   bfz_uni_prove   trace = row-major Montgomery height x width, height a power of two in
+ *                   [1, 2^23], width the chip's main width.  ch is advanced as by bfz_open (pass
+ *                   a copy to keep the caller's state).  *proof (bfz_free) is the BFU1 normal
+ *                   form of DESIGN.md; the same inputs give the same bytes.  A trace that
+ *                   violates the AIR still proves; the verifier rejects that proof.  timings
+ *                   (optional): main_commit_ms, quotient_ms, open_ms, fri_ms, total_ms.
+ *   bfz_uni_verify  host only.  Returns 0 whenever the check RAN, like bfz_verify_batch: out->ok,
+ *                   out->why ("" when ok, else the reason in the host verifier's style, e.g.
+ *                   "OOD evaluation mismatch on chip AddSub"); negative for a real error (NULL
+ *                   arguments, a refused chip).  ch is advanced; after an accepted proof it is
+ *                   the prover's final state.
+ * bfz_uni_prove and bfz_uni_verify honour bfz_set_num_queries and bfz_set_pcs_variant;
+ * BFZ_UNI_OBSERVE_DEGREE=0 drops the log degree from the transcript head (decision U1 of
+ * DESIGN.md §2). */
+int bfz_uni_info(int chip, int* num_constraints, int* degree, int* log_quotient_degree);
+int bfz_uni_prove(int chip, const uint32_t* trace, size_t height, size_t width, bfz_challenger* ch,
+                  uint8_t** proof, size_t* proof_len, bfz_timings* timings);
+int bfz_uni_verify(int chip, bfz_challenger* ch, const uint8_t* proof, size_t proof_len,
+                   bfz_verify_outcome* out);
 
 /* FRI_QUERIES (kb31_poseidon2.rs:59-62): 1..4096, or 0 = environment FRI_QUERIES / 84. */
 int bfz_set_num_queries(int num_queries);

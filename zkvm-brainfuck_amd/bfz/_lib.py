@@ -196,6 +196,11 @@ SIGNATURES = [
     ("bfz_commit_fri_sharded", c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p,
                                        ALLTOALL_FN, ALLGATHER_FN, c_void_p, POINTER(c_uint32),
                                        c_size_t, POINTER(c_size_t)]),
+    ("bfz_uni_info", c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    ("bfz_uni_prove", c_int, [c_int, POINTER(c_uint32), c_size_t, c_size_t, POINTER(Challenger),
+                              POINTER(POINTER(c_uint8)), POINTER(c_size_t), POINTER(Timings)]),
+    ("bfz_uni_verify", c_int, [c_int, POINTER(Challenger), POINTER(c_uint8), c_size_t,
+                               POINTER(VerifyOutcomeC)]),
     ("bfz_set_num_queries", c_int, [c_int]),
     ("bfz_set_pcs_variant", c_int, [c_int]),
     ("bfz_set_fault_injection", c_int, [c_int]),

@@ -803,6 +803,60 @@ CoreProver.debug_interactions = _debug_interactions_traces
 ProverClient.debug_interactions = _debug_interactions_record
 
 
+# ---- per-chip uni-STARK proofs: utils::{uni_stark_prove, uni_stark_verify}
+# (crates/core/machine/src/utils/prove.rs:97-159)
+UNI_STARK_CHIPS = (0, 2, 3, 6, 7)  # Cpu, AddSub, Jump, MemoryInstrs, IO
+
+
+@dataclass
+class UniStarkInfo:
+    """What the chip's AIR alone determines: constraints, their maximal degree and
+    log_quotient_degree = log2_ceil(degree - 1) (the proof has 2^log_quotient_degree chunks)."""
+    chip: int
+    num_constraints: int
+    degree: int
+    log_quotient_degree: int
+
+
+def uni_stark_info(chip: int) -> UniStarkInfo:
+    """bfz_uni_info (host only).  Raises for Program, Memory and Byte."""
+    k, d, l = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(lib().bfz_uni_info(int(chip), ctypes.byref(k), ctypes.byref(d), ctypes.byref(l)))
+    return UniStarkInfo(int(chip), k.value, d.value, l.value)
+
+
+def uni_stark_prove(chip: int, trace, ch: Optional[Challenger] = None,
+                    timings: Optional[_lib.Timings] = None) -> bytes:
+    """uni_stark_prove of one chip's AIR over one trace (a (height, width) uint32 array in
+    Montgomery form, as generate_traces returns) on the device; the BFU1 proof bytes.  ch (a fresh
+    DuplexChallenger when None) is advanced, as the reference's &mut challenger is."""
+    import numpy as np
+    init()
+    m = np.ascontiguousarray(trace, dtype=np.uint32)
+    if m.ndim != 2:
+        raise ValueError("uni_stark_prove: the trace must be a (height, width) matrix")
+    if ch is None:
+        ch = Challenger()
+    ptr = ctypes.POINTER(ctypes.c_uint8)()
+    plen = ctypes.c_size_t()
+    check(lib().bfz_uni_prove(int(chip), m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                              m.shape[0], m.shape[1], ctypes.byref(ch), ctypes.byref(ptr),
+                              ctypes.byref(plen), ctypes.byref(timings) if timings is not None else None))
+    return take_bytes(ptr, plen.value)
+
+
+def uni_stark_verify(chip: int, proof: bytes, ch: Optional[Challenger] = None) -> None:
+    """uni_stark_verify on the host; raises BfzError with the verifier's reason on rejection (the
+    reference returns Err).  ch (fresh when None) is advanced."""
+    if ch is None:
+        ch = Challenger()
+    buf, n = u8buf(proof)
+    out = _lib.VerifyOutcomeC()
+    check(lib().bfz_uni_verify(int(chip), ctypes.byref(ch), buf, n, ctypes.byref(out)))
+    if not out.ok:
+        raise BfzError("uni-STARK verification failed: " + out.why.decode())
+
+
 def set_num_queries(q: int) -> None:
     """FRI_QUERIES override (crates/stark/src/kb31_poseidon2.rs:59-62); 0 = environment/84."""
     check(lib().bfz_set_num_queries(int(q)))

@@ -27,6 +27,8 @@
 #include "prover.h"
 #include "tracegen.h"
 #include "verifier.h"
+#include "quotient.h"
+#include "uni_stark.h"
 #include "verify.h"
 
 struct bfz_pk {
@@ -1234,6 +1236,59 @@ struct ShardScope {  // installs the shard context for one proof
   ~ShardScope() { bfz::shard_ctx() = nullptr; }
 };
 }  // namespace
+
+namespace {
+void uni_opts(bfz::UniOptions& u) {
+  const bfz::ProveOptions o = opts();
+  u.num_queries = o.num_queries;
+  u.observe_openings = o.observe_openings;
+  u.observe_degree = bfz::uni_observe_degree_from_env();
+}
+}  // namespace
+
+int bfz_uni_info(int chip, int* num_constraints, int* degree, int* log_quotient_degree) {
+  return guarded([&] {
+    bfz::uni_air_shape_or_throw(chip, num_constraints, degree, log_quotient_degree);
+    return 0;
+  });
+}
+
+int bfz_uni_prove(int chip, const uint32_t* trace, size_t height, size_t width, bfz_challenger* ch,
+                  uint8_t** proof, size_t* len, bfz_timings* t) {
+  return guarded([&] {
+    if (!trace || !ch || !proof || !len) throw std::runtime_error("null argument");
+    bfz::Challenger c = from_c(ch);
+    bfz::StageTimes st;
+    bfz::UniOptions uo;
+    uni_opts(uo);
+    auto v = bfz::uni_prove(chip, trace, height, width, c, uo, t ? &st : nullptr);
+    if (t) {
+      std::memset(t, 0, sizeof *t);
+      fill_timings(st, t);
+    }
+    const int r = emit(std::move(v), proof, len);
+    to_c(c, ch);  // advanced as by bfz_open
+    return r;
+  });
+}
+
+int bfz_uni_verify(int chip, bfz_challenger* ch, const uint8_t* proof, size_t len,
+                   bfz_verify_outcome* out) {
+  return guarded([&] {
+    if (!ch || !out || (!proof && len)) throw std::runtime_error("null argument");
+    bfz::uni_air_shape_or_throw(chip, nullptr, nullptr, nullptr);  // a refused chip is an error
+    bfz::Challenger c = from_c(ch);
+    bfz::UniOptions uo;
+    uni_opts(uo);
+    const bfz::VerifyOutcome v = bfz::uni_verify(chip, c, proof, len, uo);
+    std::memset(out, 0, sizeof *out);
+    out->ok = v.ok;
+    out->query = v.query;
+    std::snprintf(out->why, sizeof out->why, "%s", v.why.c_str());
+    to_c(c, ch);
+    return 0;
+  });
+}
 
 int bfz_record_prove(const bfz_pk* pk, const bfz_record* rec, uint8_t** proof, size_t* len,
                      bfz_timings* t) {

@@ -15,6 +15,7 @@ using namespace kb;
 namespace {
 
 constexpr uint32_t BFZ1_MAGIC = 0x315a4642u;
+constexpr uint32_t BFU1_MAGIC = 0x31554642u;  // "BFU1"
 
 struct Out {
   std::vector<uint8_t> b;
@@ -117,6 +118,29 @@ int chip_by_name(const std::string& s) {
   throw std::runtime_error("unknown chip name in proof: " + s);
 }
 
+// The opening proof (FRI commit-phase roots, the queries, the final value, the PoW witness): the
+// same encoding in BFZ1 and BFU1.
+void read_opening_proof(In& r, ShardProof& pf) {
+  pf.commit_roots.resize(r.len(32));
+  for (Digest& d : pf.commit_roots) d = r.digest();
+  pf.queries.resize(r.len(4));
+  for (QueryProof& q : pf.queries) {
+    q.inputs.resize(r.len(8));
+    for (BatchOpening& b : q.inputs) {
+      b.rows.resize(r.len(4));
+      for (auto& row : b.rows) row = r.words();
+      b.path = r.digests();
+    }
+    q.steps.resize(r.len(20));
+    for (CommitPhaseStep& s : q.steps) {
+      s.sibling = r.ef();
+      s.path = r.digests();
+    }
+  }
+  pf.final_poly = r.ef();
+  pf.pow_witness = r.fp();
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------ BFZ1
@@ -157,26 +181,49 @@ ShardProof decode_bfz1(const uint8_t* p, size_t n) {
     c.quotient[1] = r.efs();
     c.cumsum = r.ef();
   }
-  pf.commit_roots.resize(r.len(32));
-  for (Digest& d : pf.commit_roots) d = r.digest();
-  pf.queries.resize(r.len(4));
-  for (QueryProof& q : pf.queries) {
-    q.inputs.resize(r.len(8));
-    for (BatchOpening& b : q.inputs) {
-      b.rows.resize(r.len(4));
-      for (auto& row : b.rows) row = r.words();
-      b.path = r.digests();
-    }
-    q.steps.resize(r.len(20));
-    for (CommitPhaseStep& s : q.steps) {
-      s.sibling = r.ef();
-      s.path = r.digests();
-    }
-  }
-  pf.final_poly = r.ef();
-  pf.pow_witness = r.fp();
+  read_opening_proof(r, pf);
   if (r.off != n) throw std::runtime_error("trailing bytes");
   return pf;
+}
+
+// ------------------------------------------------------------------------------------ BFU1
+UniProof decode_bfu1(const uint8_t* p, size_t n) {
+  In r{p, n};
+  UniProof u;
+  if (r.u32() != BFU1_MAGIC) throw std::runtime_error("bad magic");
+  u.chip = r.u32();
+  if (u.chip >= (uint32_t)NUM_CHIPS) throw std::runtime_error("bad chip id");
+  u.log_degree = r.u32();
+  u.pcs.main_root = r.digest();  // the trace commitment
+  u.pcs.quot_root = r.digest();  // the quotient commitment
+  u.trace_local = r.efs();
+  u.trace_next = r.efs();
+  u.chunks.resize(r.len(4));
+  for (std::vector<EF>& c : u.chunks) c = r.efs();
+  read_opening_proof(r, u.pcs);
+  if (r.off != n) throw std::runtime_error("trailing bytes");
+  return u;
+}
+
+std::vector<uint8_t> encode_bfu1(const UniProof& u, uint32_t nq, const uint32_t* query_words,
+                                 size_t nwords) {
+  Out w;
+  w.b.reserve(4 * nwords + 4096 + 32 * (u.trace_local.size() + 4 * u.chunks.size()));
+  w.u32(BFU1_MAGIC);
+  w.u32(u.chip);
+  w.u32(u.log_degree);
+  w.digest(u.pcs.main_root);
+  w.digest(u.pcs.quot_root);
+  w.efs(u.trace_local);
+  w.efs(u.trace_next);
+  w.u32((uint32_t)u.chunks.size());
+  for (const std::vector<EF>& c : u.chunks) w.efs(c);
+  w.digests(u.pcs.commit_roots);
+  w.u32(nq);
+  w.put(query_words, 4 * nwords);
+  w.ef(u.pcs.final_poly);
+  w.fp(u.pcs.pow_witness);
+  return std::move(w.b);
 }
 
 std::vector<uint8_t> encode_bfz1(const ShardProof& pf) {

@@ -59,6 +59,23 @@ struct ShardProof {
 // alternative (as_canonical_u32) kept selectable until a reference proof pins it.
 enum class FieldRepr : int { MONTGOMERY = 0, CANONICAL = 1 };
 
+// A per-chip uni-STARK proof (uni_stark.h) in the BFU1 normal form: p3_uni_stark's
+// Proof { commitments, opened_values, opening_proof } [p3-recalled] plus the chip and degree bits.
+// pcs holds the parts BFZ1 shares: main_root = the trace commitment, quot_root = the quotient
+// commitment, commit_roots / queries / final_poly / pow_witness = the opening proof.
+struct UniProof {
+  uint32_t chip = 0, log_degree = 0;
+  std::vector<EF> trace_local, trace_next;
+  std::vector<std::vector<EF>> chunks;  // 2^log_quotient_degree chunks of 4 EF
+  ShardProof pcs;
+};
+UniProof decode_bfu1(const uint8_t* p, size_t n);     // throws on malformed input
+// The BFU1 bytes of u.  The prover gathers the queries on the device already in BFZ1's query
+// encoding, so they come as nq queries in query_words (canonical words, nwords in all) and
+// u.pcs.queries is not read.
+std::vector<uint8_t> encode_bfu1(const UniProof& u, uint32_t nq, const uint32_t* query_words,
+                                 size_t nwords);
+
 ShardProof decode_bfz1(const uint8_t* p, size_t n);   // throws on malformed input
 std::vector<uint8_t> encode_bfz1(const ShardProof& pf);
 ShardProof decode_bincode(const uint8_t* p, size_t n, FieldRepr repr);

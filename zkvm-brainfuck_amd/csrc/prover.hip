@@ -88,13 +88,6 @@ bool Challenger::check_witness(int bits, uint32_t w) {
 }
 
 // ------------------------------------------------------------------------ timing
-constexpr int MAX_FRI_ROUNDS = 32;
-struct FriTail {
-  const uint32_t* root[MAX_FRI_ROUNDS];
-  int nroots;
-  const uint32_t* state;
-  const EF* fin;
-};
 // packed = [root 0 .. root MAX-1 (8 words each) | state (16) | final layer (2 EF)]; nroots may
 // be 0 (state then unused)
 __global__ void k_pack_fri_tail(FriTail t, uint32_t* __restrict__ packed) {
@@ -102,6 +95,10 @@ __global__ void k_pack_fri_tail(FriTail t, uint32_t* __restrict__ packed) {
   if (i < 8 * t.nroots) packed[i] = t.root[i >> 3][i & 7];
   if (i < 16) packed[8 * MAX_FRI_ROUNDS + i] = t.state[i];
   if (i < 8) packed[8 * MAX_FRI_ROUNDS + 16 + i] = t.fin[i >> 2].c[i & 3];
+}
+void pack_fri_tail(const FriTail& t, uint32_t* packed, hipStream_t st) {
+  hipLaunchKernelGGL(k_pack_fri_tail, dim3(1), dim3(256), 0, st, t, packed);
+  KCHECK();
 }
 
 namespace {

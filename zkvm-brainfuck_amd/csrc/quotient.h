@@ -50,6 +50,16 @@ struct QuotOut {
 };
 void quotient_into(int chip, const QuotRows& in, int logN, const QuotParams& qp, const QuotOut& out,
                    hipStream_t st, const QuotParams* qp_dev = nullptr);
+// The AIR-only quotient of one chip's trace (uni_stark.hip; k_quotient_air): mainc = the trace's
+// whole LDE (column-major, 2^logN rows), lqd = the chip's log quotient degree (0: one chunk
+// over the LDE's first half, 1: two chunks over all of it).  Of qp only alpha_pows (K powers,
+// alpha^(K-1-k)), zh_*, wn_inv and shift are read; qp_dev is the same in device memory.
+void quotient_air(int chip, int lqd, const uint32_t* mainc, int logN, const QuotParams& qp,
+                  const QuotParams* qp_dev, const QuotOut& out, hipStream_t st);
+// Constraints Air::eval_air<chip> emits, their maximal degree and log2_ceil(degree - 1)
+// (chip.rs:82-87), computed from air.h.  false: the chip has no AIR constraints of its own.
+bool uni_air_shape(int chip, int* num_constraints, int* degree, int* log_quotient_degree);
+
 // The quotient challenge on the device after the LogUp commit (see k_challenge_quot): ch is the
 // device sponge (updated), root the permutation root, cums the chips' cumulative sums, pc the
 // LogUp challenges; qps[k]'s perm_alpha / beta_pows / cumsum and apows[k] (K[k] powers) are

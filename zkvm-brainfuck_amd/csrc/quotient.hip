@@ -233,6 +233,87 @@ void quotient_into(int chip, const QuotRows& in, int logN, const QuotParams& qp,
   }
 }
 
+// The AIR-only quotient of ONE chip's trace: p3_uni_stark's quotient_values [p3-recalled] under
+// the reference's uni-STARK builders, where send / receive are no-ops (air/builder.rs:232-239,
+// 273-275) -- Air::eval_air<CHIP> alone, no preprocessed and no permutation columns.  The
+// quotient domain is 3 H_(n 2^LQD): with LQD = 1 every row of the 2n-row LDE (as k_quotient),
+// with LQD = 0 the even natural indices, which are the LDE's first n storage rows (bitrev of an
+// even index has its top bit clear); there i is always even, so Z_H is the constant 3^n - 1
+// (zh_even) and sel_inv is read at the same position t.  The next row is quotient index
+// j + 2^LQD, i.e. LDE natural index i + 2 in both shapes.  Output as k_quotient: chunk
+// (t >> log n) at row t mod n, the bit-reversed order of chunk j's domain 3 w_2n^j H_n.
+template <int CHIP, int LQD>
+__global__ __launch_bounds__(256, 3) void k_quotient_air(const uint32_t* __restrict__ mainc,
+                                                         int logN,
+                                                         const QuotParams* __restrict__ qpp,
+                                                         const uint32_t* __restrict__ twf,
+                                                         const uint32_t* __restrict__ sel_inv,
+                                                         QuotOut qo) {
+  const QuotParams qp = *qpp;
+  constexpr int MW = QMAIN_W[CHIP];
+  const size_t N = (size_t)1 << logN, n = N >> 1;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (n << LQD)) return;
+  const uint32_t i = dbitrev((uint32_t)t, logN);
+  const uint32_t inext = (i + 2) & (uint32_t)(N - 1);
+  const uint32_t vt = (uint32_t)t * 4u, vn = dbitrev(inext, logN) * 4u;
+
+  uint32_t L[MW], Nx[MW];  // the same per-column buffer loads as k_quotient
+#pragma unroll
+  for (int c = 0; c < MW; c++) {
+    const __amdgpu_buffer_rsrc_t r = rsrc_of(mainc + (size_t)c * N);
+    L[c] = ld_b(r, vt, 0);
+    Nx[c] = ld_b(r, vn, 0);
+  }
+  const uint32_t none[1] = {0};  // no preprocessed trace (p3_uni_stark takes none)
+
+  const uint32_t x = quot_point(i, (uint32_t)n, qp.shift, twf);
+  const uint32_t zh = (i & 1) ? qp.zh_odd : qp.zh_even;
+  const uint32_t zh_inv = (i & 1) ? qp.zh_odd_inv : qp.zh_even_inv;
+  const uint32_t a = msub(x, ONE), b = msub(x, qp.wn_inv);
+  const uint32_t zi = mmul(zh, sel_inv[t]);
+  const uint32_t is_first = mmul(zi, b), is_last = mmul(zi, a), is_trans = b;
+
+  PowAcc acc{{0, 0, 0, 0}, 0,
+             (const __attribute__((address_space(4))) uint32_t*)qp.alpha_pows, 0};
+  Air<BaseOps, PowAcc> air{L, Nx, none, none, is_first, is_last, is_trans, acc};
+  air.template eval_air<CHIP>();
+  const EF q = ef_mul_base(acc.value(), zh_inv);
+  const size_t chunk = LQD ? t >> (logN - 1) : 0, pos = t & (n - 1);
+#pragma unroll
+  for (int e = 0; e < 4; e++) qo.chunk[chunk][e * qo.stride + pos] = q.c[e];
+}
+
+template <int CHIP>
+static void launch_qa(int lqd, const uint32_t* mainc, int logN, const QuotParams* qp_dev,
+                      const uint32_t* sel, const QuotOut& qo, hipStream_t st) {
+  const size_t count = ((size_t)1 << (logN - 1)) << lqd;
+  const uint32_t* twf = (const uint32_t*)twiddles().fwd();
+  if (lqd == 0)
+    hipLaunchKernelGGL((k_quotient_air<CHIP, 0>), dim3(ceil_div(count, 256)), dim3(256), 0, st,
+                       mainc, logN, qp_dev, twf, sel, qo);
+  else
+    hipLaunchKernelGGL((k_quotient_air<CHIP, 1>), dim3(ceil_div(count, 256)), dim3(256), 0, st,
+                       mainc, logN, qp_dev, twf, sel, qo);
+  KCHECK();
+}
+
+void quotient_air(int chip, int lqd, const uint32_t* mainc, int logN, const QuotParams& qp,
+                  const QuotParams* qp_dev, const QuotOut& qout, hipStream_t st) {
+  if (lqd < 0 || lqd > 1) throw std::runtime_error("quotient_air: log quotient degree not 0 or 1");
+  if (logN < 1 || logN > 24) throw std::runtime_error("quotient_air: bad LDE height");
+  twiddles().ensure(logN);
+  const uint32_t* sel = sel_inv_table(logN, qp, st);
+  switch (chip) {
+    case CHIP_CPU: launch_qa<CHIP_CPU>(lqd, mainc, logN, qp_dev, sel, qout, st); break;
+    case CHIP_ADDSUB: launch_qa<CHIP_ADDSUB>(lqd, mainc, logN, qp_dev, sel, qout, st); break;
+    case CHIP_JUMP: launch_qa<CHIP_JUMP>(lqd, mainc, logN, qp_dev, sel, qout, st); break;
+    case CHIP_MEMINSTRS: launch_qa<CHIP_MEMINSTRS>(lqd, mainc, logN, qp_dev, sel, qout, st); break;
+    case CHIP_IO: launch_qa<CHIP_IO>(lqd, mainc, logN, qp_dev, sel, qout, st); break;
+    default: throw std::runtime_error("quotient_air: the chip has no AIR constraints");
+  }
+}
+
 // The quotient challenge on the device (challenger.h): the sponge observes the permutation
 // root and every chip's cumulative sum, samples alpha (prover.rs:336-342); each chip's alpha
 // powers alpha^(K-1-j) and the challenge fields of its QuotParams are written.
@@ -326,6 +407,68 @@ int num_constraints(int chip) {
   if (chip < 0 || chip >= NUM_CHIPS) return 0;
   return counts[chip];
 }
+
+// Degree of each AIR constraint, by running eval_air over degrees instead of values: the rules
+// of SymbolicExpression::degree_multiple [p3-recalled] -- a trace variable 1, a constant 0,
+// is_first_row / is_last_row 1, is_transition 0, add / sub the maximum, mul the sum, neg the
+// identity.
+struct DegOps {
+  using T = int;
+  static KB_HD T add(T a, T b) { return a > b ? a : b; }
+  static KB_HD T sub(T a, T b) { return a > b ? a : b; }
+  static KB_HD T mul(T a, T b) { return a + b; }
+  static KB_HD T neg(T a) { return a; }
+  static KB_HD T cst(uint32_t) { return 0; }
+};
+struct DegAcc {
+  int max = 0;
+  void emit(int d) {
+    if (d > max) max = d;
+  }
+};
+
+// K from CountAcc over eval_air alone (count_chip above adds the LogUp constraints), the degree
+// from a second evaluation over degrees.
+template <int CHIP>
+static void air_shape(int* K, int* degree) {
+  EF z[64];
+  for (auto& e : z) e = kb::ef_zero();
+  CountAcc count;
+  Air<ExtOps, CountAcc> counted{z, z, z, z, z[0], z[0], z[0], count};
+  counted.template eval_air<CHIP>();
+  *K = count.n;
+  int one[64];
+  for (int& v : one) v = 1;
+  DegAcc acc;
+  Air<DegOps, DegAcc> air{one, one, one, one, 1, 1, 0, acc};
+  air.template eval_air<CHIP>();
+  *degree = acc.max;
+}
+
+bool uni_air_shape(int chip, int* K, int* degree, int* lqd) {
+  int k = 0, d = 0;
+  switch (chip) {
+    case CHIP_CPU: air_shape<CHIP_CPU>(&k, &d); break;
+    case CHIP_ADDSUB: air_shape<CHIP_ADDSUB>(&k, &d); break;
+    case CHIP_JUMP: air_shape<CHIP_JUMP>(&k, &d); break;
+    case CHIP_MEMINSTRS: air_shape<CHIP_MEMINSTRS>(&k, &d); break;
+    case CHIP_IO: air_shape<CHIP_IO>(&k, &d); break;
+    default: return false;  // Program, Memory, Byte: no AIR constraints of their own
+  }
+  int l = 0;  // log2_ceil(d - 1), at least 0 (chip.rs:82-87)
+  while ((1 << l) < d - 1) l++;
+  if (K) *K = k;
+  if (degree) *degree = d;
+  if (lqd) *lqd = l;
+  return true;
+}
+
+static PreloadKernels preload_quotient_air{
+    (const void*)&k_quotient_air<0, 0>, (const void*)&k_quotient_air<0, 1>,
+    (const void*)&k_quotient_air<2, 0>, (const void*)&k_quotient_air<2, 1>,
+    (const void*)&k_quotient_air<3, 0>, (const void*)&k_quotient_air<3, 1>,
+    (const void*)&k_quotient_air<6, 0>, (const void*)&k_quotient_air<6, 1>,
+    (const void*)&k_quotient_air<7, 0>, (const void*)&k_quotient_air<7, 1>};
 
 // kernels a proof launches (gpu.h PreloadKernels)
 static PreloadKernels preload_quotient{

@@ -1,0 +1,40 @@
+// Per-chip uni-STARK proofs: bf_core_machine::utils::{uni_stark_prove, uni_stark_verify}
+// (crates/core/machine/src/utils/prove.rs:97-159), i.e. p3_uni_stark::{prove, verify}
+// [p3-recalled] of ONE chip's AIR over one trace with the machine prover's PCS and challenger.
+// Under the uni-STARK builders a chip's send / receive are no-ops (air/builder.rs:232-239,
+// 273-275): what is proven is Air::eval_air<CHIP> (air.h) and nothing else.  DESIGN.md §2
+// (decisions U1-U6) and §4 (the BFU1 normal form, the kernel).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "prover.h"
+#include "verifier.h"
+
+namespace bfz {
+
+// Decision U1: the transcript starts with observe(F(log degree)) (1, default) or with the trace
+// commitment alone (0, p3 before the degree was bound); environment BFZ_UNI_OBSERVE_DEGREE.
+bool uni_observe_degree_from_env();
+
+struct UniOptions {
+  int num_queries = 84;
+  bool observe_openings = true;  // decision D1
+  bool observe_degree = true;    // decision U1
+};
+
+// uni_air_shape (quotient.h) for a chip that has one; throws the refusal the C ABI reports for a
+// bad index and for Program, Memory and Byte.  Any output pointer may be null.
+void uni_air_shape_or_throw(int chip, int* num_constraints, int* degree, int* log_quotient_degree);
+
+// trace: row-major Montgomery height x width on the host.  ch is advanced to the state after
+// the whole opening (as open_main's `after`).  Returns the BFU1 bytes.  The API lock is held.
+std::vector<uint8_t> uni_prove(int chip, const uint32_t* trace, size_t height, size_t width,
+                               Challenger& ch, const UniOptions& opt, StageTimes* times);
+
+// Host verifier (verifier.cpp).  ch is advanced as far as the check got; on acceptance it is the
+// prover's final state.
+VerifyOutcome uni_verify(int chip, Challenger& ch, const uint8_t* proof, size_t len,
+                         const UniOptions& opt);
+
+}  // namespace bfz

@@ -18,6 +18,8 @@
 #include "machine.h"
 #include "poseidon2.h"
 #include "prover.h"
+#include "quotient.h"
+#include "uni_stark.h"
 #include "verify.h"
 
 namespace bfz {
@@ -162,12 +164,50 @@ struct ShardState {
   std::vector<ChipOpen> co;
   EF pa, pb, alpha, zeta, fri_alpha, final_poly;
   std::vector<VMat> rounds[4];
+  int nrounds = 4;  // input rounds in use: 4 in a machine proof, 2 in a per-chip uni-STARK proof
   const uint32_t* roots[4] = {};
   std::vector<EF> betas;
   uint32_t ncommit = 0, nq = 0;
   int log_max = 0;
   std::vector<size_t> index;  // the sampled index of every query
 };
+
+// The transcript of TwoAdicFriPcs::verify [p3-recalled] once S.rounds holds the opened values:
+// the opened values (D1), the batching challenge, the commit-phase roots and their betas, the
+// final value, the PoW check, the query indices.
+void pcs_transcript(ShardState& S, Challenger& ch, bool observe_openings, int num_queries) {
+  const ShardProof& pf = *S.pf;
+  const std::vector<VMat>* rounds = S.rounds;
+  if (observe_openings)  // decision D1: opened values enter the transcript
+    for (int rr = 0; rr < S.nrounds; rr++)
+      for (const VMat& m : rounds[rr])
+        for (int p = 0; p < m.np; p++)
+          for (int c = 0; c < m.w; c++) ch.observe_ef((*m.v[p])[c]);
+  S.fri_alpha = ch.sample_ef();
+  const uint32_t ncommit = S.ncommit = (uint32_t)pf.commit_roots.size();
+  if (ncommit > 30) throw std::runtime_error("too many FRI rounds");
+  const int log_max = S.log_max = (int)ncommit + LOG_BLOWUP;
+  {  // the commit phase folds the tallest LDE down to 2^LOG_BLOWUP: every height must fit
+    int lh_max = 0;
+    for (int rr = 0; rr < S.nrounds; rr++)
+      for (const VMat& m : rounds[rr]) lh_max = std::max(lh_max, m.log_n + LOG_BLOWUP);
+    if (lh_max != log_max) throw std::runtime_error("FRI round count does not match the tallest matrix");
+  }
+  S.betas.resize(ncommit);
+  for (uint32_t i = 0; i < ncommit; i++) {
+    ch.observe_digest(pf.commit_roots[i].data());
+    S.betas[i] = ch.sample_ef();
+  }
+  const uint32_t nq = S.nq = (uint32_t)pf.queries.size();
+  if ((int)nq != num_queries) throw std::runtime_error("wrong number of queries");
+  S.final_poly = pf.final_poly;
+  ch.observe_ef(S.final_poly);
+  if (!ch.check_witness(POW_BITS, from_mont(pf.pow_witness))) throw std::runtime_error("bad PoW witness");
+  // nothing but the indices is drawn from the transcript from here on, and no check of the
+  // query loop touches it: sampling them all first changes no outcome
+  S.index.resize(nq);
+  for (uint32_t q = 0; q < nq; q++) S.index[q] = ch.sample_bits(log_max);
+}
 
 void before_queries(const std::string& src, const uint32_t vk_commit[8], const ShardProof& pf,
                     const VerifyOptions& opt, ShardState& S) {
@@ -275,39 +315,11 @@ void before_queries(const std::string& src, const uint32_t vk_commit[8], const S
         rounds[3].push_back(VMat{c.log_n, mmul(to_mont(3), k ? w2n : ONE), 4, 1, {zeta, zeta},
                                  {&c.q[k], &c.q[k]}});
     }
-    if (opt.observe_openings)  // decision D1: opened values enter the transcript
-      for (int rr = 0; rr < 4; rr++)
-        for (const VMat& m : rounds[rr])
-          for (int p = 0; p < m.np; p++)
-            for (int c = 0; c < m.w; c++) ch.observe_ef((*m.v[p])[c]);
-    S.fri_alpha = ch.sample_ef();
-    const uint32_t ncommit = S.ncommit = (uint32_t)pf.commit_roots.size();
-    if (ncommit > 30) throw std::runtime_error("too many FRI rounds");
-    const int log_max = S.log_max = (int)ncommit + LOG_BLOWUP;
-    {  // the commit phase folds the tallest LDE down to 2^LOG_BLOWUP: every height must fit
-      int lh_max = 0;
-      for (int rr = 0; rr < 4; rr++)
-        for (const VMat& m : rounds[rr]) lh_max = std::max(lh_max, m.log_n + LOG_BLOWUP);
-      if (lh_max != log_max) throw std::runtime_error("FRI round count does not match the tallest matrix");
-    }
-    S.betas.resize(ncommit);
-    for (uint32_t i = 0; i < ncommit; i++) {
-      ch.observe_digest(pf.commit_roots[i].data());
-      S.betas[i] = ch.sample_ef();
-    }
-    const uint32_t nq = S.nq = (uint32_t)pf.queries.size();
-    if ((int)nq != opt.num_queries) throw std::runtime_error("wrong number of queries");
-    S.final_poly = pf.final_poly;
-    ch.observe_ef(S.final_poly);
-    if (!ch.check_witness(POW_BITS, from_mont(pf.pow_witness))) throw std::runtime_error("bad PoW witness");
     S.roots[0] = vk_commit;
     S.roots[1] = main_root;
     S.roots[2] = perm_root;
     S.roots[3] = quot_root;
-    // nothing but the indices is drawn from the transcript from here on, and no check of the
-    // query loop touches it: sampling them all first changes no outcome
-    S.index.resize(nq);
-    for (uint32_t q = 0; q < nq; q++) S.index[q] = ch.sample_bits(log_max);
+    pcs_transcript(S, ch, opt.observe_openings, opt.num_queries);
   }
 }
 
@@ -325,9 +337,9 @@ void check_query(const ShardState& S, uint32_t q) {
     {
       const QueryProof& qp = pf.queries[q];
       const size_t index = S.index[q];
-      if (qp.inputs.size() != 4) throw std::runtime_error("bad round count");
+      if (qp.inputs.size() != (size_t)S.nrounds) throw std::runtime_error("bad round count");
       std::map<int, std::pair<EF, EF>> ro;  // log height -> (alpha_pow, ro)
-      for (int rr = 0; rr < 4; rr++) {
+      for (int rr = 0; rr < S.nrounds; rr++) {
         const BatchOpening& bo = qp.inputs[rr];
         const size_t nm = bo.rows.size();
         if (nm != rounds[rr].size()) throw std::runtime_error("bad matrix count");
@@ -765,6 +777,107 @@ std::vector<VerifyOutcome> verify_batch(const std::string& src, const uint32_t v
     i0 = i1;
   }
   return out;
+}
+
+// ------------------------------------------------------------------ per-chip uni-STARK proofs
+namespace {
+template <int CHIP>
+EF fold_air(const std::vector<EF>& ml, const std::vector<EF>& mn, const EF& first, const EF& last,
+            const EF& trans, const EF& alpha) {
+  HornerAcc acc;
+  acc.alpha = alpha;
+  static const EF zero1[1] = {ef_zero()};  // no preprocessed trace
+  Air<ExtOps, HornerAcc> air{ml.data(), mn.data(), zero1, zero1, first, last, trans, acc};
+  air.template eval_air<CHIP>();
+  return acc.acc;
+}
+EF fold_air_any(int chip, const std::vector<EF>& ml, const std::vector<EF>& mn, const EF& f,
+                const EF& l, const EF& t, const EF& al) {
+  switch (chip) {
+    case CHIP_CPU: return fold_air<CHIP_CPU>(ml, mn, f, l, t, al);
+    case CHIP_ADDSUB: return fold_air<CHIP_ADDSUB>(ml, mn, f, l, t, al);
+    case CHIP_JUMP: return fold_air<CHIP_JUMP>(ml, mn, f, l, t, al);
+    case CHIP_MEMINSTRS: return fold_air<CHIP_MEMINSTRS>(ml, mn, f, l, t, al);
+    case CHIP_IO: return fold_air<CHIP_IO>(ml, mn, f, l, t, al);
+  }
+  throw std::runtime_error("bad chip");
+}
+}  // namespace
+
+// p3_uni_stark::verify [p3-recalled] as utils::uni_stark_verify calls it (utils/prove.rs:129-159):
+// shapes from the chip table (never from the proof), the transcript replay, PCS verify, the
+// quotient recomposed at zeta from its chunks, the selectors at zeta, the AIR folded with alpha.
+VerifyOutcome uni_verify(int chip, Challenger& ch, const uint8_t* proof, size_t len,
+                         const UniOptions& opt) {
+  VerifyOutcome o;
+  try {
+    int K = 0, degree = 0, lqd = 0;
+    if (!uni_air_shape(chip, &K, &degree, &lqd) || lqd > 1)
+      throw std::runtime_error("chip has no uni-STARK AIR");
+    const UniProof u = decode_bfu1(proof, len);
+    if ((int)u.chip != chip) throw std::runtime_error("proof is for another chip");
+    // unsigned: a huge word must not become a negative shift count below
+    if (u.log_degree > 23) throw std::runtime_error("log degree out of range");
+    const int log_n = (int)u.log_degree, nchunks = 1 << lqd;
+    const size_t w = (size_t)CHIP_INFO[chip].main_w;
+    if (u.trace_local.size() != w || u.trace_next.size() != w || u.chunks.size() != (size_t)nchunks)
+      throw std::runtime_error("opened-value shape mismatch");
+    for (const std::vector<EF>& c : u.chunks)
+      if (c.size() != 4) throw std::runtime_error("opened-value shape mismatch");
+
+    // ---- transcript head (U1, U2)
+    if (opt.observe_degree) ch.observe(to_mont((uint32_t)log_n));
+    ch.observe_digest(u.pcs.main_root.data());
+    const EF alpha = ch.sample_ef();
+    ch.observe_digest(u.pcs.quot_root.data());
+    const EF zeta = ch.sample_ef();
+
+    // ---- PCS verify: [trace: (zeta, zeta w_n)], [chunk j: (zeta)] on 3 w_(n 2^lqd)^j H_n
+    ShardState S;
+    S.pf = &u.pcs;
+    S.nrounds = 2;
+    S.zeta = zeta;
+    S.roots[0] = u.pcs.main_root.data();
+    S.roots[1] = u.pcs.quot_root.data();
+    S.rounds[0].push_back(VMat{log_n, ONE, (int)w, 2, {zeta, ef_mul_base(zeta, two_adic_gen(log_n))},
+                               {&u.trace_local, &u.trace_next}});
+    const uint32_t wq = two_adic_gen(log_n + lqd);
+    std::vector<uint32_t> sh(nchunks);
+    for (int j = 0; j < nchunks; j++) {
+      sh[j] = mmul(to_mont(3), mpow(wq, (uint64_t)j));
+      S.rounds[1].push_back(VMat{log_n, sh[j], 4, 1, {zeta, zeta}, {&u.chunks[j], &u.chunks[j]}});
+    }
+    pcs_transcript(S, ch, opt.observe_openings, opt.num_queries);
+    for (uint32_t q = 0; q < S.nq; q++) {
+      o.query = (int)q;
+      check_query(S, q);
+    }
+    o.query = -1;
+
+    // ---- the quotient at zeta from its chunks, the selectors, the folded constraints
+    EF quot = ef_zero();
+    for (int a = 0; a < nchunks; a++) {
+      EF zps = ef_one();
+      for (int b = 0; b < nchunks; b++)
+        if (b != a)
+          zps = ef_mul(zps, ef_mul(zp_at(log_n, sh[b], zeta), ef_inv(zp_at(log_n, sh[b], ef_base(sh[a])))));
+      for (int e = 0; e < 4; e++) quot = ef_add(quot, ef_mul(ef_mul(zps, monomial(e)), u.chunks[a][e]));
+    }
+    const uint32_t gn_inv = minv(two_adic_gen(log_n));
+    EF zh = zeta;
+    for (int k = 0; k < log_n; k++) zh = ef_mul(zh, zh);
+    zh = ef_sub(zh, ef_one());
+    const EF first = ef_mul(zh, ef_inv(ef_sub(zeta, ef_one())));
+    const EF last = ef_mul(zh, ef_inv(ef_sub(zeta, ef_base(gn_inv))));
+    const EF trans = ef_sub(zeta, ef_base(gn_inv));
+    const EF folded = fold_air_any(chip, u.trace_local, u.trace_next, first, last, trans, alpha);
+    if (!ef_eq(ef_mul(folded, ef_inv(zh)), quot))
+      throw std::runtime_error(std::string("OOD evaluation mismatch on chip ") + CHIP_INFO[chip].name);
+    o.ok = true;
+  } catch (const std::exception& e) {
+    o.why = e.what();
+  }
+  return o;
 }
 
 // Columns a chip's constraints read at the next row (quotient.rs:41-42), found by perturbing
