@@ -270,6 +270,20 @@ pub struct bfz_verify_outcome {
     pub why: [c_char; 120],
 }
 
+/// The AIR-only row check of one chip (`bfz_uni_check`): what `p3_uni_stark::prove` checks in a
+/// debug build (crates/core/machine/src/utils/prove.rs:97-112).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bfz_uni_check_result {
+    pub chip: i32,
+    pub num_constraints: i32,
+    pub height: u64,
+    pub failing_rows: u64,
+    pub first_row: i64,
+    pub first_constraint: i32,
+    pub _pad: i32,
+}
+
 pub type bfz_allgather_fn =
     Option<unsafe extern "C" fn(ctx: *mut c_void, send: *const c_void, bytes: usize, recv: *mut c_void) -> c_int>;
 pub type bfz_allreduce_u32_fn = Option<unsafe extern "C" fn(ctx: *mut c_void, data: *mut u32, n: usize) -> c_int>;
@@ -395,6 +409,20 @@ extern "C" {
                          timings: *mut bfz_timings) -> c_int;
     pub fn bfz_uni_verify(chip: c_int, ch: *mut bfz_challenger, proof: *const u8, proof_len: usize,
                           out: *mut bfz_verify_outcome) -> c_int;
+    /// The debug-build row check of `uni_stark_prove` (utils/prove.rs:97-112, debug.rs:43-94).
+    pub fn bfz_uni_check(chip: c_int, trace: *const u32, height: usize, width: usize,
+                         on_device: c_int, out: *mut bfz_uni_check_result,
+                         first_fail_per_row: *mut i32) -> c_int;
+    pub fn bfz_record_uni_check(rec: *const bfz_record, chip: c_int,
+                                out: *mut bfz_uni_check_result) -> c_int;
+    /// `uni_stark_prove` of one chip of a device record; 1 when the record lacks the chip.
+    pub fn bfz_record_uni_prove(rec: *const bfz_record, chip: c_int, ch: *mut bfz_challenger,
+                                proof: *mut *mut u8, proof_len: *mut usize,
+                                timings: *mut bfz_timings) -> c_int;
+    /// `uni_stark_verify` of many proofs, each with its own chip and challenger.
+    pub fn bfz_uni_verify_batch(chips: *const c_int, chs: *mut bfz_challenger,
+                                proofs: *const *const u8, lens: *const usize, n: usize,
+                                on_device: c_int, out: *mut bfz_verify_outcome) -> c_int;
 
     pub fn bfz_set_num_queries(num_queries: c_int) -> c_int;
     pub fn bfz_set_pcs_variant(observe_openings: c_int) -> c_int;

@@ -25,6 +25,13 @@
  *                                                         crates/core/machine/src/utils/prove.rs:97-127
  *   bfz_uni_verify   utils::uni_stark_verify -> p3_uni_stark::verify
  *                                                         crates/core/machine/src/utils/prove.rs:129-159
+ *   bfz_uni_check    the row check of p3_uni_stark::prove in a debug build (Air<DebugConstraintBuilder>)
+ *                                                         crates/core/machine/src/utils/prove.rs:97-112,
+ *                                                         crates/stark/src/debug.rs:43-94
+ *   bfz_record_uni_prove   uni_stark_prove on a chip trace the device generated
+ *                                                         crates/core/machine/src/utils/prove.rs:97-127
+ *   bfz_uni_verify_batch   uni_stark_verify of many proofs, query phase on the device
+ *                                                         crates/core/machine/src/utils/prove.rs:129-159
  *
  * Conventions: field elements are uint32_t in MONTGOMERY form (x * 2^32 mod p), i.e.
  * byte-identical to a Rust `[KoalaBear]` slice; matrices are row-major.  Every function
@@ -581,7 +588,8 @@ int bfz_setup_host(const char* elf, bfz_pk** pk);
  *                   [1, 2^23], width the chip's main width.  ch is advanced as by bfz_open (pass
  *                   a copy to keep the caller's state).  *proof (bfz_free) is the BFU1 normal
  *                   form of DESIGN.md; the same inputs give the same bytes.  A trace that
- *                   violates the AIR still proves; the verifier rejects that proof.  timings
+ *                   violates the AIR still proves; the verifier rejects that proof, and
+ *                   bfz_uni_check (below) names the row and the constraint.  timings
  *                   (optional): main_commit_ms, quotient_ms, open_ms, fri_ms, total_ms.
  *   bfz_uni_verify  host only.  Returns 0 whenever the check RAN, like bfz_verify_batch: out->ok,
  *                   out->why ("" when ok, else the reason in the host verifier's style, e.g.
@@ -597,6 +605,56 @@ int bfz_uni_prove(int chip, const uint32_t* trace, size_t height, size_t width, 
 int bfz_uni_verify(int chip, bfz_challenger* ch, const uint8_t* proof, size_t proof_len,
                    bfz_verify_outcome* out);
 
+/* The debug half of uni_stark_prove.  In a debug build the reference's uni_stark_prove requires
+ * Air<DebugConstraintBuilder> (crates/core/machine/src/utils/prove.rs:97-112): p3_uni_stark::prove
+ * [p3-recalled] checks every row of the trace against the AIR and panics at the first failing
+ * constraint.  bfz_uni_check is that check with the row semantics of crates/stark/src/debug.rs:43-94
+ * (row i local, row (i + 1) mod height next, is_first = [i == 0], is_last = [i == height - 1],
+ * is_transition = 1 - is_last; a 1-row trace is its own next row).  Only the chip's own AIR
+ * constraints are evaluated -- no LogUp constraint, so no permutation trace, challenge or
+ * cumulative sum is needed (bfz_check_chip is the check that has them) -- and a constraint is named
+ * by its 0-based position among them, 0 .. K-1 with the K of bfz_uni_info (for AddSub the indices
+ * 0-7 of bfz_chip_check's numbering).  Like the other checks it returns 0 whenever the check RAN
+ * and reports the outcome in failing_rows; chips, arguments, refusals and their messages are
+ * bfz_uni_prove's (a wrong width, a height that is no power of two, a word >= p: negative status).
+ *   bfz_uni_check         trace as for bfz_uni_prove.  on_device = 0 runs the same row function on
+ *                         the host, single-threaded, no device needed; 1 uploads the trace and runs
+ *                         the check kernel.  first_fail_per_row (optional, `height` entries, natural
+ *                         row order) receives each row's first failing index, or -1.
+ *   bfz_record_uni_check  the chip's trace of a device record, generated on the device as
+ *                         bfz_record_prove does and checked where it is.  Returns 1 when the record
+ *                         does not include the chip (as bfz_trace). */
+typedef struct {
+  int32_t chip, num_constraints;   /* K of bfz_uni_info: the AIR's constraints only */
+  uint64_t height, failing_rows;
+  int64_t first_row;               /* smallest failing row, natural order; -1 if none */
+  int32_t first_constraint, _pad;  /* first failing index at first_row, in eval_air's emission order */
+} bfz_uni_check_result;
+int bfz_uni_check(int chip, const uint32_t* trace, size_t height, size_t width, int on_device,
+                  bfz_uni_check_result* out, int32_t* first_fail_per_row /* optional, natural order */);
+int bfz_record_uni_check(const bfz_record* rec, int chip, bfz_uni_check_result* out);
+
+/* uni_stark_prove (crates/core/machine/src/utils/prove.rs:97-127) of one chip of a device record:
+ * the record's traces are generated on the device as bfz_record_prove does (all chips; one is
+ * used) and the chip's evaluations are proven where they are -- no upload, no transpose, no copy.
+ * The proof is byte-identical to bfz_uni_prove on the same chip's host trace (bfz_trace), and ch
+ * ends in the same state.  Returns 1 when the record does not include the chip.  timings
+ * (optional): trace_ms (the trace generation) and the stages of bfz_uni_prove. */
+int bfz_record_uni_prove(const bfz_record* rec, int chip, bfz_challenger* ch,
+                         uint8_t** proof, size_t* proof_len, bfz_timings* timings);
+
+/* uni_stark_verify (crates/core/machine/src/utils/prove.rs:129-159) of n proofs with
+ * bfz_verify_batch's contract: proof i is of chip chips[i] and is checked against its own
+ * challenger chs[i], which is advanced as by bfz_uni_verify.  Returns 0 whenever the check RAN
+ * (n = 0 is a no-op); negative for a real error (NULL arguments, a refused chip, on_device = 1
+ * without a bound device).  on_device = 0 is bfz_uni_verify proof by proof; on_device = 1 runs
+ * everything before and after the query loops on the host and all the proofs' query loops in one
+ * batched device pass (the kernels of bfz_verify_batch, two input rounds per proof), with the same
+ * (ok, query, why) and the same ending challengers for the same bytes.  Honours
+ * bfz_set_num_queries, bfz_set_pcs_variant, BFZ_UNI_OBSERVE_DEGREE and fault-injection bit 1. */
+int bfz_uni_verify_batch(const int* chips, bfz_challenger* chs, const uint8_t* const* proofs,
+                         const size_t* lens, size_t n, int on_device, bfz_verify_outcome* out);
+
 /* FRI_QUERIES (kb31_poseidon2.rs:59-62): 1..4096, or 0 = environment FRI_QUERIES / 84. */
 int bfz_set_num_queries(int num_queries);
 
@@ -608,11 +666,11 @@ int bfz_set_pcs_variant(int observe_openings);
 
 /* Test-only fault injection, no reference counterpart: bit 0 perturbs the device challenger's
  * uploaded sponge state, so the host's replay of the device-sampled challenges must fail the
- * proof with "device transcript diverged" (tests/test_gpu.py).  Bit 1 makes bfz_verify_batch with
- * on_device = 1 run its host side only (stages, packing, the queries the packing keeps on the
- * host) with a stand-in for the kernels that reports no failure and needs no device, so that side
- * is testable without a GPU (tests/test_verify_batch.py); its verdicts are then not a
- * verification.  Bit 2 cuts the key hash of the device path of bfz_*_debug_interactions to its low
+ * proof with "device transcript diverged" (tests/test_gpu.py).  Bit 1 makes bfz_verify_batch and
+ * bfz_uni_verify_batch with on_device = 1 run their host side only (stages, packing, the queries
+ * the packing keeps on the host) with a stand-in for the kernels that reports no failure and needs
+ * no device, so that side is testable without a GPU (tests/test_verify_batch.py,
+ * tests/test_uni_device.py); its verdicts are then not a verification.  Bit 2 cuts the key hash of the device path of bfz_*_debug_interactions to its low
  * 12 bits before anything uses it (home slot and tag alike), so distinct keys share tags and the
  * multi-round path runs; verdicts and records must not change.  0 (default) = off. */
 int bfz_set_fault_injection(int mask);

@@ -90,6 +90,13 @@ class LookupReportC(ctypes.Structure):
                 ("rounds", c_uint32), ("tag_collisions", c_uint32), ("table_bytes", c_uint64)]
 
 
+class UniCheckC(ctypes.Structure):
+    """bfz_uni_check_result: the AIR-only row check of one chip."""
+    _fields_ = [("chip", c_int32), ("num_constraints", c_int32), ("height", c_uint64),
+                ("failing_rows", c_uint64), ("first_row", c_int64), ("first_constraint", c_int32),
+                ("_pad", c_int32)]
+
+
 class VerifyOutcomeC(ctypes.Structure):
     """bfz_verify_outcome: one proof's verdict from bfz_verify_batch."""
     _fields_ = [("ok", c_int32), ("query", c_int32), ("why", ctypes.c_char * 120)]
@@ -201,6 +208,13 @@ SIGNATURES = [
                               POINTER(POINTER(c_uint8)), POINTER(c_size_t), POINTER(Timings)]),
     ("bfz_uni_verify", c_int, [c_int, POINTER(Challenger), POINTER(c_uint8), c_size_t,
                                POINTER(VerifyOutcomeC)]),
+    ("bfz_uni_check", c_int, [c_int, POINTER(c_uint32), c_size_t, c_size_t, c_int,
+                              POINTER(UniCheckC), POINTER(c_int32)]),
+    ("bfz_record_uni_check", c_int, [c_void_p, c_int, POINTER(UniCheckC)]),
+    ("bfz_record_uni_prove", c_int, [c_void_p, c_int, POINTER(Challenger), POINTER(POINTER(c_uint8)),
+                                     POINTER(c_size_t), POINTER(Timings)]),
+    ("bfz_uni_verify_batch", c_int, [POINTER(c_int), POINTER(Challenger), POINTER(POINTER(c_uint8)),
+                                     POINTER(c_size_t), c_size_t, c_int, POINTER(VerifyOutcomeC)]),
     ("bfz_set_num_queries", c_int, [c_int]),
     ("bfz_set_pcs_variant", c_int, [c_int]),
     ("bfz_set_fault_injection", c_int, [c_int]),
@@ -277,5 +291,5 @@ def take_bytes(ptr, n: int) -> bytes:
 
 
 __all__ = ["lib", "check", "init", "u8buf", "take_bytes", "BfzError", "Timings", "Events", "LIB_PATH",
-           "ChipCheck", "DebugReportC", "VerifyOutcomeC", "LookupDiscrepancyC", "LookupReportC",
+           "ChipCheck", "DebugReportC", "VerifyOutcomeC", "UniCheckC", "LookupDiscrepancyC", "LookupReportC",
            "SIGNATURES", "byref"]

@@ -26,6 +26,13 @@ and of the reference's debug mode (crates/stark/src/machine.rs:288-387, debug.rs
     lookups = prover.debug_interactions(pk, traces)  # (lookup/debug.rs:125-196): per-key
     print(lookups)                                   # send-receive discrepancies
 
+and of the per-chip uni-STARK helpers (crates/core/machine/src/utils/prove.rs:97-159):
+
+    res = uni_stark_check(chip, trace)           # the debug-build row check of uni_stark_prove
+    proof = uni_stark_prove(chip, trace, check=True)
+    proofs = client.uni_stark_prove_record(pk, stdin)    # from the traces the device generates
+    outcomes = uni_stark_verify_batch(chips, proofs)     # query phase on the device
+
 Errors raise (the reference returns Err / panics in the same places).  Proving runs on the GPU
 through libbfz; verification runs the host verifier compiled into the same library.
 """
@@ -33,7 +40,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 from . import _lib
 from ._lib import BfzError, Challenger, check, init, lib, take_bytes, u8buf
@@ -825,23 +832,82 @@ def uni_stark_info(chip: int) -> UniStarkInfo:
     return UniStarkInfo(int(chip), k.value, d.value, l.value)
 
 
+@dataclass
+class UniCheckResult:
+    """bfz_uni_check_result: the AIR-only row check of one chip.  Constraint indices count the
+    chip's own AIR constraints alone (0 .. num_constraints - 1, the K of uni_stark_info)."""
+    chip: int
+    height: int
+    num_constraints: int
+    failing_rows: int
+    first_row: int
+    first_constraint: int
+    first_fail_per_row: Optional[object] = None  # numpy int32[height], natural order, when asked for
+
+    @property
+    def ok(self) -> bool:
+        return self.failing_rows == 0
+
+    def __str__(self) -> str:
+        if not self.failing_rows:
+            return f"{CHIPS[self.chip]}: {self.height} row(s) ok"
+        return (f"{CHIPS[self.chip]}: {self.failing_rows} failing row(s); first: row {self.first_row}, "
+                f"AIR constraint {self.first_constraint} of {self.num_constraints}")
+
+
+def _uni_check_result(c, per_row=None) -> UniCheckResult:
+    return UniCheckResult(chip=c.chip, height=c.height, num_constraints=c.num_constraints,
+                          failing_rows=c.failing_rows, first_row=c.first_row,
+                          first_constraint=c.first_constraint, first_fail_per_row=per_row)
+
+
+def uni_stark_check(chip: int, trace, on_device: bool = True, per_row: bool = False) -> UniCheckResult:
+    """The row check p3_uni_stark::prove runs in a debug build (utils/prove.rs:97-112) over one
+    trace (as uni_stark_prove takes it): every row against the chip's AIR constraints alone
+    (bfz_uni_check).  A failing trace does not raise; the result names the first failing row and
+    constraint.  on_device=False runs the same row function on the host (no GPU needed)."""
+    import numpy as np
+    if on_device:
+        init()
+    m = np.ascontiguousarray(trace, dtype=np.uint32)
+    if m.ndim != 2:
+        raise ValueError("uni_stark_check: the trace must be a (height, width) matrix")
+    out = _lib.UniCheckC()
+    rows = np.zeros(m.shape[0], dtype=np.int32) if per_row else None
+    check(lib().bfz_uni_check(int(chip), m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                              m.shape[0], m.shape[1], int(bool(on_device)), ctypes.byref(out),
+                              rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if per_row else None))
+    return _uni_check_result(out, rows)
+
+
+def _raise_if_failing(res: UniCheckResult) -> None:
+    if res.failing_rows:
+        raise BfzError(f"uni_stark_prove: the trace violates the AIR: {res}")
+
+
 def uni_stark_prove(chip: int, trace, ch: Optional[Challenger] = None,
-                    timings: Optional[_lib.Timings] = None) -> bytes:
+                    timings: Optional[_lib.Timings] = None, check: bool = False) -> bytes:
     """uni_stark_prove of one chip's AIR over one trace (a (height, width) uint32 array in
     Montgomery form, as generate_traces returns) on the device; the BFU1 proof bytes.  ch (a fresh
-    DuplexChallenger when None) is advanced, as the reference's &mut challenger is."""
+    DuplexChallenger when None) is advanced, as the reference's &mut challenger is.  check=True
+    runs uni_stark_check first and raises BfzError naming the chip, row and constraint when a row
+    fails (the reference's debug-build behaviour); by default an invalid trace still proves."""
     import numpy as np
     init()
     m = np.ascontiguousarray(trace, dtype=np.uint32)
     if m.ndim != 2:
         raise ValueError("uni_stark_prove: the trace must be a (height, width) matrix")
+    if check:
+        _raise_if_failing(uni_stark_check(chip, m, on_device=True))
     if ch is None:
         ch = Challenger()
     ptr = ctypes.POINTER(ctypes.c_uint8)()
     plen = ctypes.c_size_t()
-    check(lib().bfz_uni_prove(int(chip), m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                              m.shape[0], m.shape[1], ctypes.byref(ch), ctypes.byref(ptr),
-                              ctypes.byref(plen), ctypes.byref(timings) if timings is not None else None))
+    # (the parameter `check` hides the module's function here)
+    _lib.check(lib().bfz_uni_prove(
+        int(chip), m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), m.shape[0], m.shape[1],
+        ctypes.byref(ch), ctypes.byref(ptr), ctypes.byref(plen),
+        ctypes.byref(timings) if timings is not None else None))
     return take_bytes(ptr, plen.value)
 
 
@@ -855,6 +921,74 @@ def uni_stark_verify(chip: int, proof: bytes, ch: Optional[Challenger] = None) -
     check(lib().bfz_uni_verify(int(chip), ctypes.byref(ch), buf, n, ctypes.byref(out)))
     if not out.ok:
         raise BfzError("uni-STARK verification failed: " + out.why.decode())
+
+
+def uni_stark_verify_batch(chips, proofs, on_device: bool = True, chs=None) -> List[VerifyOutcome]:
+    """uni_stark_verify of many proofs (bfz_uni_verify_batch): proofs[i] is a BFU1 proof of chip
+    chips[i], checked against chs[i] (fresh challengers when None; each is advanced).  A rejected
+    proof does not raise.  on_device=True runs all the proofs' query phases in one batched GPU
+    pass; False is uni_stark_verify's host verifier proof by proof.  Both give the same outcomes."""
+    raw = [bytes(p) for p in proofs]
+    k = len(raw)
+    if len(chips) != k or (chs is not None and len(chs) != k):
+        raise ValueError("uni_stark_verify_batch: one chip (and one challenger) per proof")
+    if on_device:
+        init()
+    bufs = [u8buf(x) for x in raw]
+    arr = (ctypes.POINTER(ctypes.c_uint8) * max(k, 1))(
+        *[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b, _ in bufs])
+    lens = (ctypes.c_size_t * max(k, 1))(*[n for _, n in bufs])
+    cids = (ctypes.c_int * max(k, 1))(*[int(c) for c in chips])
+    carr = (Challenger * max(k, 1))()
+    if chs is not None:
+        for i, c in enumerate(chs):
+            ctypes.memmove(ctypes.byref(carr[i]), ctypes.byref(c), ctypes.sizeof(Challenger))
+    out = (_lib.VerifyOutcomeC * max(k, 1))()
+    check(lib().bfz_uni_verify_batch(cids, carr, arr, lens, k, int(bool(on_device)), out))
+    if chs is not None:
+        for i, c in enumerate(chs):
+            ctypes.memmove(ctypes.byref(c), ctypes.byref(carr[i]), ctypes.sizeof(Challenger))
+    return [VerifyOutcome(ok=bool(out[i].ok), query=out[i].query, why=out[i].why.decode())
+            for i in range(k)]
+
+
+def _uni_stark_prove_record(self, pk: BfProvingKey, stdin, chips=UNI_STARK_CHIPS,
+                            check: bool = False) -> Dict[int, bytes]:
+    """uni_stark_prove of the chips of (pk's program, stdin) from the traces the device generates:
+    one bfz_record_new, then bfz_record_uni_prove per chip, each from a fresh challenger.  Chips
+    the record does not include are left out of the result.  check=True runs
+    bfz_record_uni_check before each proof and raises as uni_stark_prove(check=True) does."""
+    init(self.device)
+    buf, n = u8buf(bytes(stdin))
+    rec = ctypes.c_void_p()
+    cyc = ctypes.c_uint64()
+    _lib.check(lib().bfz_record_new(ctypes.c_void_p(pk.handle), buf, n, ctypes.byref(rec),
+                                    ctypes.byref(cyc)))
+    out = {}
+    try:
+        for chip in chips:
+            if check:
+                res = _lib.UniCheckC()
+                rc = lib().bfz_record_uni_check(rec, int(chip), ctypes.byref(res))
+                if rc == 1:
+                    continue
+                _lib.check(rc)
+                _raise_if_failing(_uni_check_result(res))
+            ch = Challenger()
+            ptr = ctypes.POINTER(ctypes.c_uint8)()
+            plen = ctypes.c_size_t()
+            rc = lib().bfz_record_uni_prove(rec, int(chip), ctypes.byref(ch), ctypes.byref(ptr),
+                                            ctypes.byref(plen), None)
+            if rc == 1:
+                continue
+            _lib.check(rc)
+            out[int(chip)] = take_bytes(ptr, plen.value)
+    finally:
+        lib().bfz_record_free(rec)
+    return out
+
+
+ProverClient.uni_stark_prove_record = _uni_stark_prove_record
 
 
 def set_num_queries(q: int) -> None:

@@ -852,6 +852,24 @@ int bfz_verify(const char* elf, const uint32_t vk_commit[8], const uint8_t* proo
   });
 }
 
+}  // extern "C"
+namespace {
+// The query phase of bfz_verify_batch and bfz_uni_verify_batch with on_device = 1.
+void query_runner_device(const bfz::QueryBatch& b, uint32_t* keys) {
+  bfz::verify_queries_device(b, keys, bfz::stream());
+}
+// The stand-in runs no kernel and leaves every key at "no failure": what remains is the host side
+// of the device path (stages, packing, the queries the packing keeps on the host).
+void query_runner_none(const bfz::QueryBatch&, uint32_t*) {}
+void to_c(const bfz::VerifyOutcome& v, bfz_verify_outcome* o) {
+  std::memset(o, 0, sizeof *o);
+  o->ok = v.ok;
+  o->query = v.query;
+  std::snprintf(o->why, sizeof o->why, "%s", v.why.c_str());
+}
+}  // namespace
+extern "C" {
+
 int bfz_verify_batch(const char* elf, const uint32_t vk_commit[8], const uint8_t* const* proofs,
                      const size_t* lens, size_t n, int on_device, bfz_verify_outcome* out) {
   return guarded([&] {
@@ -867,20 +885,10 @@ int bfz_verify_batch(const char* elf, const uint32_t vk_commit[8], const uint8_t
     bfz::VerifyOptions vo;
     vo.num_queries = o.num_queries;
     vo.observe_openings = o.observe_openings;
-    const bfz::QueryRunner run = [](const bfz::QueryBatch& b, uint32_t* keys) {
-      bfz::verify_queries_device(b, keys, bfz::stream());
-    };
-    // the stand-in runs no kernel and leaves every key at "no failure": what remains is the host
-    // side of the device path (stages, packing, the queries the packing keeps on the host)
-    const bfz::QueryRunner none = [](const bfz::QueryBatch&, uint32_t*) {};
-    const std::vector<bfz::VerifyOutcome> v =
-        bfz::verify_batch(elf, vk_commit, proofs, lens, n, vo, standin ? none : on_device ? run : nullptr);
-    for (size_t i = 0; i < n; i++) {
-      std::memset(&out[i], 0, sizeof out[i]);
-      out[i].ok = v[i].ok;
-      out[i].query = v[i].query;
-      std::snprintf(out[i].why, sizeof out[i].why, "%s", v[i].why.c_str());
-    }
+    const std::vector<bfz::VerifyOutcome> v = bfz::verify_batch(
+        elf, vk_commit, proofs, lens, n, vo,
+        standin ? query_runner_none : on_device ? query_runner_device : nullptr);
+    for (size_t i = 0; i < n; i++) to_c(v[i], &out[i]);
     return 0;
   });
 }
@@ -1280,12 +1288,134 @@ int bfz_uni_verify(int chip, bfz_challenger* ch, const uint8_t* proof, size_t le
     bfz::Challenger c = from_c(ch);
     bfz::UniOptions uo;
     uni_opts(uo);
-    const bfz::VerifyOutcome v = bfz::uni_verify(chip, c, proof, len, uo);
-    std::memset(out, 0, sizeof *out);
-    out->ok = v.ok;
-    out->query = v.query;
-    std::snprintf(out->why, sizeof out->why, "%s", v.why.c_str());
+    to_c(bfz::uni_verify(chip, c, proof, len, uo), out);
     to_c(c, ch);
+    return 0;
+  });
+}
+
+}  // extern "C"
+namespace {
+void to_c(const bfz::ChipCheck& c, bfz_uni_check_result* o) {
+  static_assert(sizeof(bfz_uni_check_result) == 40, "bfz_uni_check_result has no gaps");
+  std::memset(o, 0, sizeof *o);
+  o->chip = c.chip;
+  o->num_constraints = c.num_constraints;
+  o->height = c.height;
+  o->failing_rows = c.failing_rows;
+  o->first_row = c.first_row;
+  o->first_constraint = c.first_constraint;
+}
+// The record's traces, generated as bfz_record_prove does, and the position of `chip` among them
+// (-1: the record does not include it).  *ms (optional): the generation's time on the stream.
+int record_chip_traces(const bfz_record* rec, int chip, bfz::DeviceTraces& dt, double* ms) {
+  hipStream_t st = bfz::stream();
+  hipEvent_t a = nullptr, b = nullptr;
+  if (ms) {
+    HIP_CHECK(hipEventCreate(&a));
+    HIP_CHECK(hipEventCreate(&b));
+    HIP_CHECK(hipEventRecord(a, st));
+  }
+  bfz::generate_traces_device(rec->ev, dt, st);
+  if (ms) {
+    float f = 0;
+    HIP_CHECK(hipEventRecord(b, st));
+    HIP_CHECK(hipEventSynchronize(b));
+    HIP_CHECK(hipEventElapsedTime(&f, a, b));
+    *ms = f;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+  }
+  for (size_t k = 0; k < dt.chips.size(); k++)
+    if (dt.chips[k] == chip) return (int)k;
+  return -1;
+}
+}  // namespace
+extern "C" {
+
+int bfz_uni_check(int chip, const uint32_t* trace, size_t height, size_t width, int on_device,
+                  bfz_uni_check_result* out, int32_t* first_fail_per_row) {
+  return guarded([&] {
+    if (!trace || !out) throw std::runtime_error("null argument");
+    bfz::uni_dims_or_throw(chip, height, width);
+    bfz::ChipCheck cc;
+    if (!on_device) {
+      // mmul needs words < p, and the check compares reduced words with 0
+      for (size_t i = 0; i < height * width; i++)
+        if (trace[i] >= kb::P) bfz::uni_noncanonical_throw(chip);
+      bfz::check_air_host(chip, trace, height, cc, first_fail_per_row);
+    } else {
+      hipStream_t st = bfz::stream();
+      const bfz::DBuf<uint32_t> evals = bfz::uni_upload_trace(chip, trace, height, st);
+      bfz::check_air_resident(chip, evals.p, height, cc, first_fail_per_row, st);
+    }
+    to_c(cc, out);
+    return 0;
+  });
+}
+
+int bfz_record_uni_check(const bfz_record* rec, int chip, bfz_uni_check_result* out) {
+  return guarded([&] {
+    if (!rec || !out) throw std::runtime_error("null argument");
+    bfz::uni_air_shape_or_throw(chip, nullptr, nullptr, nullptr);
+    bfz::DeviceTraces dt;
+    const int k = record_chip_traces(rec, chip, dt, nullptr);
+    if (k < 0) return 1;
+    bfz::ChipCheck cc;
+    bfz::check_air_resident(chip, dt.evals[k].p, dt.heights[k], cc, nullptr, bfz::stream());
+    to_c(cc, out);
+    return 0;
+  });
+}
+
+int bfz_record_uni_prove(const bfz_record* rec, int chip, bfz_challenger* ch, uint8_t** proof,
+                         size_t* len, bfz_timings* t) {
+  return guarded([&] {
+    if (!rec || !ch || !proof || !len) throw std::runtime_error("null argument");
+    bfz::uni_air_shape_or_throw(chip, nullptr, nullptr, nullptr);
+    bfz::Challenger c = from_c(ch);
+    bfz::StageTimes st;
+    bfz::UniOptions uo;
+    uni_opts(uo);
+    // every chip's trace is generated (one launch sequence, as bfz_record_prove); one is used
+    bfz::DeviceTraces dt;
+    const int k = record_chip_traces(rec, chip, dt, t ? &st.trace : nullptr);
+    if (k < 0) return 1;
+    auto v = bfz::uni_prove_evals(chip, dt.evals[k].p, dt.heights[k], c, uo, t ? &st : nullptr);
+    if (t) {
+      st.total += st.trace;
+      std::memset(t, 0, sizeof *t);
+      fill_timings(st, t);
+    }
+    const int r = emit(std::move(v), proof, len);
+    to_c(c, ch);  // advanced as by bfz_uni_prove
+    return r;
+  });
+}
+
+int bfz_uni_verify_batch(const int* chips, bfz_challenger* chs, const uint8_t* const* proofs,
+                         const size_t* lens, size_t n, int on_device, bfz_verify_outcome* out) {
+  return guarded([&] {
+    if (n == 0) return 0;
+    if (!chips || !chs || !proofs || !lens || !out) throw std::runtime_error("null argument");
+    for (size_t i = 0; i < n; i++) {
+      if (!proofs[i] && lens[i]) throw std::runtime_error("null proof");
+      bfz::uni_air_shape_or_throw(chips[i], nullptr, nullptr, nullptr);  // a refused chip is an error
+    }
+    const bool standin = on_device && (g_fault & 2);  // bfz_set_fault_injection bit 1 (tests only)
+    if (on_device && !standin && g_bound < 0)
+      throw std::runtime_error("uni_verify_batch: no device bound (bfz_init) for on_device = 1");
+    bfz::UniOptions uo;
+    uni_opts(uo);
+    std::vector<bfz::Challenger> cs(n);
+    for (size_t i = 0; i < n; i++) cs[i] = from_c(&chs[i]);
+    const std::vector<bfz::VerifyOutcome> v = bfz::uni_verify_batch(
+        chips, cs.data(), proofs, lens, n, uo,
+        standin ? query_runner_none : on_device ? query_runner_device : nullptr);
+    for (size_t i = 0; i < n; i++) {
+      to_c(v[i], &out[i]);
+      to_c(cs[i], &chs[i]);
+    }
     return 0;
   });
 }

@@ -47,7 +47,10 @@ struct FirstFailAcc {
 
 // Chip::eval on one row of the trace domain (debug.rs:43-97): the first failing constraint
 // index, or -1.  L / N: main local / next; PL / PN: preprocessed; pl / pn: permutation (EF).
-template <int CHIP>
+// PERM = false stops after the chip's own AIR constraints (indices 0 .. K_air - 1, the K of
+// uni_air_shape): what p3_uni_stark's debug-build prove checks (utils/prove.rs:97-112), where
+// send / receive are no-ops; the permutation arguments are then not read.
+template <int CHIP, bool PERM = true>
 KB_HD int check_row(const uint32_t* L, const uint32_t* N, const uint32_t* PL, const uint32_t* PN,
                     const EF* pl, const EF* pn, bool is_first, bool is_last, const EF& alpha,
                     const EF* beta_pows, const EF& cumsum) {
@@ -56,9 +59,17 @@ KB_HD int check_row(const uint32_t* L, const uint32_t* N, const uint32_t* PL, co
   FirstFailAcc acc;
   Air<BaseOps, FirstFailAcc> air{L, N, PL, PN, first, last, trans, acc};
   air.template eval_air<CHIP>();
-  air.template eval_perm<CHIP>(pl, pn, alpha, beta_pows, cumsum, kb::ef_base(first),
-                               kb::ef_base(last), kb::ef_base(trans));
+  if constexpr (PERM)
+    air.template eval_perm<CHIP>(pl, pn, alpha, beta_pows, cumsum, kb::ef_base(first),
+                                 kb::ef_base(last), kb::ef_base(trans));
   return acc.first;
+}
+// The AIR-only row of a chip without a preprocessed trace (the uni-STARK chips).
+template <int CHIP>
+KB_HD int check_row_air(const uint32_t* L, const uint32_t* N, bool is_first, bool is_last) {
+  const uint32_t none[1] = {0};
+  const EF z = kb::ef_zero();
+  return check_row<CHIP, false>(L, N, none, none, nullptr, nullptr, is_first, is_last, z, nullptr, z);
 }
 
 // One row's interactions for the balance table (lookup/debug.rs:79-116): per LookupKind the sum
@@ -172,6 +183,14 @@ void check_chip_device(int chip, const uint32_t* mainc, const uint32_t* prepc,
                        const uint32_t* permc, size_t h, const PermChallenges* ch_dev,
                        const EF* cumsum_dev, unsigned long long* res_dev, int32_t* per_row_dev,
                        hipStream_t st);
+// The AIR-only check of one uni-STARK chip (Cpu, AddSub, Jump, MemoryInstrs, IO; others throw as
+// uni_air_shape_or_throw): out.num_constraints = the K of uni_air_shape, num_batches = 0.
+// Host: row-major natural-order trace.  Device: a device-resident column-major bit-reversed
+// trace (gpu.h LAYOUT); the kernel's two result words and its per-row array are brought back
+// (syncs st).  per_row (optional, host, h entries) is in natural row order in both.
+void check_air_host(int chip, const uint32_t* main, size_t h, ChipCheck& out, int32_t* per_row);
+void check_air_resident(int chip, const uint32_t* mainc, size_t h, ChipCheck& out, int32_t* per_row,
+                        hipStream_t st);
 // chip, height, K and the number of LogUp batches of a result.
 void fill_chip_header(int chip, size_t h, ChipCheck& out);
 // Fills out.{failing_rows, first_row, first_constraint} from the two downloaded words.

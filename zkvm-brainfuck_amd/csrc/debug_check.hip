@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "quotient.h"
+#include "uni_stark.h"
 
 namespace bfz {
 
@@ -49,6 +50,37 @@ __device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
     v = o < v ? o : v;
   }
   return v;
+}
+
+// The block's failing rows into res: wave minimum of row * K + index and ballot popcount, block
+// minimum over the four waves, then one atomicMin / atomicAdd per block that has a failure.
+// Every thread of the block calls it (idx < 0: the row holds, or there is no row).
+__device__ __forceinline__ void reduce_failures(int idx, uint32_t i, int K,
+                                                unsigned long long* __restrict__ res) {
+  const bool fail = idx >= 0;
+  const unsigned long long key =
+      wave_min(fail ? (unsigned long long)i * (unsigned)K + (unsigned)idx : ~0ull);
+  const unsigned long long votes = __ballot(fail);
+  __shared__ unsigned long long s_key[4];
+  __shared__ uint32_t s_cnt[4];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    s_key[wave] = key;
+    s_cnt[wave] = (uint32_t)__popcll(votes);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long k = s_key[0];
+    uint32_t cnt = s_cnt[0];
+    for (int w = 1; w < 4; w++) {
+      k = s_key[w] < k ? s_key[w] : k;
+      cnt += s_cnt[w];
+    }
+    if (cnt) {
+      atomicMin(&res[0], k);
+      atomicAdd(&res[1], (unsigned long long)cnt);
+    }
+  }
 }
 
 // ------------------------------------------------------------------------ row check
@@ -96,30 +128,7 @@ __global__ __launch_bounds__(256) void k_check(const uint32_t* __restrict__ main
     idx = check_row<CHIP>(L, Nx, PL, PN, pl, pn, i == 0, i == n - 1, ch.alpha, ch.beta_pows, cs);
     if (per_row) per_row[t] = idx;
   }
-  const bool fail = idx >= 0;
-  const unsigned long long key =
-      wave_min(fail ? (unsigned long long)i * (unsigned)K + (unsigned)idx : ~0ull);
-  const unsigned long long votes = __ballot(fail);
-  __shared__ unsigned long long s_key[4];
-  __shared__ uint32_t s_cnt[4];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    s_key[wave] = key;
-    s_cnt[wave] = (uint32_t)__popcll(votes);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long k = s_key[0];
-    uint32_t cnt = s_cnt[0];
-    for (int w = 1; w < 4; w++) {
-      k = s_key[w] < k ? s_key[w] : k;
-      cnt += s_cnt[w];
-    }
-    if (cnt) {
-      atomicMin(&res[0], k);
-      atomicAdd(&res[1], (unsigned long long)cnt);
-    }
-  }
+  reduce_failures(idx, i, K, res);
 }
 
 template <int CHIP>
@@ -171,6 +180,101 @@ void decode_check_result(const unsigned long long res[2], ChipCheck& out) {
     out.first_constraint = (int)(res[0] % (unsigned)out.num_constraints);
   }
 }
+
+// ------------------------------------------------------------------------ AIR-only row check
+// k_check_air<CHIP>: k_check without the preprocessed and permutation columns and without the
+// challenges -- Air::eval_air<CHIP> alone, what p3_uni_stark::prove checks in a debug build
+// (crates/core/machine/src/utils/prove.rs:97-112).  K is the chip's AIR constraint count.
+template <int CHIP>
+__global__ __launch_bounds__(256) void k_check_air(const uint32_t* __restrict__ mainc, uint32_t n,
+                                                   int logn, int K,
+                                                   unsigned long long* __restrict__ res,
+                                                   int32_t* __restrict__ per_row) {
+  constexpr int MW = DBG_MAIN_W[CHIP];
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  int idx = -1;
+  uint32_t i = 0;
+  if (t < n) {  // (no early return: every thread takes part in the block reduction)
+    i = dbitrev(t, logn);
+    const uint32_t tn = dbitrev((i + 1) & (n - 1), logn);  // h = 1: the row is its own next
+    const uint32_t vt = t * 4u, vn = tn * 4u;               // t, tn < n <= 2^23
+    uint32_t L[MW], Nx[MW];
+#pragma unroll
+    for (int c = 0; c < MW; c++) {
+      const __amdgpu_buffer_rsrc_t r = rsrc_of(mainc + (size_t)c * n);
+      L[c] = ld_b(r, vt, 0);
+      Nx[c] = ld_b(r, vn, 0);
+    }
+    idx = check_row_air<CHIP>(L, Nx, i == 0, i == n - 1);
+    if (per_row) per_row[t] = idx;
+  }
+  reduce_failures(idx, i, K, res);
+}
+
+template <int CHIP>
+static void rows_air_host(const uint32_t* main, size_t h, ChipCheck& out, int32_t* per_row) {
+  constexpr int MW = DBG_MAIN_W[CHIP];
+  out.failing_rows = 0;
+  out.first_row = -1;
+  out.first_constraint = -1;
+  for (size_t i = 0; i < h; i++) {
+    const size_t nx = (i + 1) & (h - 1);
+    const int idx = check_row_air<CHIP>(main + i * MW, main + nx * MW, i == 0, i == h - 1);
+    if (per_row) per_row[i] = idx;
+    if (idx >= 0 && out.failing_rows++ == 0) {
+      out.first_row = (int64_t)i;
+      out.first_constraint = idx;
+    }
+  }
+}
+
+static void fill_air_header(int chip, size_t h, ChipCheck& out) {
+  int K = 0;
+  uni_air_shape_or_throw(chip, &K, nullptr, nullptr);
+  check_shape(chip, h);
+  out = ChipCheck();
+  out.chip = chip;
+  out.height = h;
+  out.num_constraints = K;
+}
+
+#define BFZ_AIR_CHIPS(X) X(CHIP_CPU) X(CHIP_ADDSUB) X(CHIP_JUMP) X(CHIP_MEMINSTRS) X(CHIP_IO)
+
+void check_air_host(int chip, const uint32_t* main, size_t h, ChipCheck& out, int32_t* per_row) {
+  fill_air_header(chip, h, out);
+#define BFZ_AIR_CASE(C) \
+  case C: rows_air_host<C>(main, h, out, per_row); break;
+  switch (chip) { BFZ_AIR_CHIPS(BFZ_AIR_CASE) }
+#undef BFZ_AIR_CASE
+}
+
+void check_air_resident(int chip, const uint32_t* mainc, size_t h, ChipCheck& out, int32_t* per_row,
+                        hipStream_t st) {
+  fill_air_header(chip, h, out);
+  DBuf<unsigned long long> resd(2);
+  DBuf<int32_t> rowd;
+  if (per_row) rowd.reset(h);
+  unsigned long long res[2] = {~0ull, 0};
+  HIP_CHECK(hipMemcpyAsync(resd.p, res, sizeof(res), hipMemcpyHostToDevice, st));
+#define BFZ_AIR_CASE(C)                                                                        \
+  case C:                                                                                      \
+    hipLaunchKernelGGL(k_check_air<C>, dim3(ceil_div(h, 256)), dim3(256), 0, st, mainc,        \
+                       (uint32_t)h, log2i(h), out.num_constraints, resd.p, rowd.p);            \
+    break;
+  switch (chip) { BFZ_AIR_CHIPS(BFZ_AIR_CASE) }
+#undef BFZ_AIR_CASE
+  KCHECK();
+  std::vector<int32_t> rows(per_row ? h : 0);
+  HIP_CHECK(hipMemcpyAsync(res, resd.p, sizeof(res), hipMemcpyDeviceToHost, st));
+  if (per_row) HIP_CHECK(hipMemcpyAsync(rows.data(), rowd.p, h * 4, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  decode_check_result(res, out);
+  if (per_row) {
+    const int logh = log2i(h);
+    for (size_t r = 0; r < h; r++) per_row[r] = rows[bitrev32((uint32_t)r, logh)];  // storage -> natural
+  }
+}
+#undef BFZ_AIR_CHIPS
 
 // ------------------------------------------------------------------------ host path
 template <int CHIP>

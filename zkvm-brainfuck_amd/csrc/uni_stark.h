@@ -32,9 +32,31 @@ void uni_air_shape_or_throw(int chip, int* num_constraints, int* degree, int* lo
 std::vector<uint8_t> uni_prove(int chip, const uint32_t* trace, size_t height, size_t width,
                                Challenger& ch, const UniOptions& opt, StageTimes* times);
 
+// The same from device evaluations: evals = n x main_w of the chip, column-major and bit-reversed
+// (gpu.h LAYOUT, what generate_traces_device leaves in DeviceTraces::evals), read in place.  Same
+// bytes and same ending challenger as uni_prove on the same trace.
+std::vector<uint8_t> uni_prove_evals(int chip, const uint32_t* evals, size_t n, Challenger& ch,
+                                     const UniOptions& opt, StageTimes* times);
+
+// The input checks every uni-STARK call shares, with uni_prove's messages: the chip
+// (uni_air_shape_or_throw), a constraint degree above 3, the width, the height.
+void uni_dims_or_throw(int chip, size_t height, size_t width);
+[[noreturn]] void uni_noncanonical_throw(int chip);  // a trace word >= p
+// uni_prove's upload: the row-major host trace to the device, refused when a word is >= p
+// (syncs st), transposed into the library layout.
+DBuf<uint32_t> uni_upload_trace(int chip, const uint32_t* trace, size_t n, hipStream_t st);
+
 // Host verifier (verifier.cpp).  ch is advanced as far as the check got; on acceptance it is the
 // prover's final state.
 VerifyOutcome uni_verify(int chip, Challenger& ch, const uint8_t* proof, size_t len,
                          const UniOptions& opt);
+
+// n BFU1 proofs, proof i of chip chips[i] against challenger chs[i] (advanced), with
+// verify_batch's contract (verifier.h): run_queries == nullptr is uni_verify proof by proof;
+// otherwise the query loops are packed into one QueryBatch and handed to run_queries, and the
+// outcomes and ending challengers are the same.
+std::vector<VerifyOutcome> uni_verify_batch(const int* chips, Challenger* chs,
+                                            const uint8_t* const* proofs, const size_t* lens,
+                                            size_t n, const UniOptions& opt, QueryRunner run_queries);
 
 }  // namespace bfz

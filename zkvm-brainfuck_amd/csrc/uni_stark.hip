@@ -80,54 +80,93 @@ struct StageClock {  // stage times of a timed call: events on the prover stream
     for (auto& m : marks) (void)hipEventDestroy(m.first);
   }
 };
+
+struct Rewind {  // the pinned upload arena is rewound when the call is done (as ProofScope)
+  hipStream_t st;
+  ~Rewind() {
+    (void)hipStreamSynchronize(st);
+    staging_reset();
+  }
+};
+
+std::vector<uint8_t> prove_core(int chip, const uint32_t* evals, size_t n, Challenger& ch_io,
+                                const UniOptions& opt, StageTimes* tms, StageClock& clock);
 }  // namespace
 
-std::vector<uint8_t> uni_prove(int chip, const uint32_t* trace, size_t height, size_t width,
-                               Challenger& ch_io, const UniOptions& opt, StageTimes* times) {
-  if (api_lock_depth() == 0) throw std::logic_error("uni_prove called outside the bfz API lock");
-  int K = 0, degree = 0, lqd = 0;
-  uni_air_shape_or_throw(chip, &K, &degree, &lqd);
-  if (lqd > 1) throw std::runtime_error("uni_stark: constraint degree above 3 is not supported");
-  if (!trace) throw std::runtime_error("uni_stark: null trace");
-  const int w = CHIP_INFO[chip].main_w;
-  if ((size_t)w != width)
+void uni_dims_or_throw(int chip, size_t height, size_t width) {
+  int k = 0, degree = 0, l = 0;
+  uni_air_shape_or_throw(chip, &k, &degree, &l);
+  if (l > 1) throw std::runtime_error("uni_stark: constraint degree above 3 is not supported");
+  if ((size_t)CHIP_INFO[chip].main_w != width)
     throw std::runtime_error(std::string("uni_stark: width mismatch for ") + CHIP_INFO[chip].name);
-  const size_t n = height;
-  if (n < 1 || (n & (n - 1)) || n > ((size_t)1 << 23))
+  if (height < 1 || (height & (height - 1)) || height > ((size_t)1 << 23))
     throw std::runtime_error(std::string("uni_stark: height not a power of two in [1, 2^23] for ") +
                              CHIP_INFO[chip].name);
+}
+
+void uni_noncanonical_throw(int chip) {
+  throw std::runtime_error(std::string("uni_stark: non-canonical field word (>= p) in ") +
+                           CHIP_INFO[chip].name);
+}
+
+DBuf<uint32_t> uni_upload_trace(int chip, const uint32_t* trace, size_t n, hipStream_t st) {
+  const int w = CHIP_INFO[chip].main_w;
+  DBuf<uint32_t> evals(n * (size_t)w), rm(n * (size_t)w);
+  upload_bulk(rm.p, trace, n * (size_t)w * 4, st);
+  // KoalaBear words are Montgomery residues < p; a larger word breaks mmul's b < p bound
+  if (count_noncanonical(rm.p, n * (size_t)w, st)) uni_noncanonical_throw(chip);
+  transpose_bitrev(rm.p, n, w, evals.p, st);
+  return evals;
+}
+
+// The host-trace front: checks, upload, transpose (all inside the main_commit stage time).
+std::vector<uint8_t> uni_prove(int chip, const uint32_t* trace, size_t height, size_t width,
+                               Challenger& ch, const UniOptions& opt, StageTimes* times) {
+  if (api_lock_depth() == 0) throw std::logic_error("uni_prove called outside the bfz API lock");
+  if (!trace) throw std::runtime_error("uni_stark: null trace");
+  uni_dims_or_throw(chip, height, width);
   if (opt.num_queries < 1 || opt.num_queries > 4096) throw std::runtime_error("uni_stark: bad query count");
+  hipStream_t st = stream();
+  Rewind rewind{st};
+  StageTimes local;
+  StageClock clock(times != nullptr, st);
+  const DBuf<uint32_t> evals = uni_upload_trace(chip, trace, height, st);
+  return prove_core(chip, evals.p, height, ch, opt, times ? times : &local, clock);
+}
+
+// The device front: the evaluations are where they are, nothing is uploaded, transposed or copied.
+std::vector<uint8_t> uni_prove_evals(int chip, const uint32_t* evals, size_t n, Challenger& ch,
+                                     const UniOptions& opt, StageTimes* times) {
+  if (api_lock_depth() == 0) throw std::logic_error("uni_prove called outside the bfz API lock");
+  if (!evals) throw std::runtime_error("uni_stark: null trace");
+  uni_air_shape_or_throw(chip, nullptr, nullptr, nullptr);  // before CHIP_INFO is indexed
+  uni_dims_or_throw(chip, n, (size_t)CHIP_INFO[chip].main_w);
+  if (opt.num_queries < 1 || opt.num_queries > 4096) throw std::runtime_error("uni_stark: bad query count");
+  hipStream_t st = stream();
+  Rewind rewind{st};
+  StageTimes local;
+  StageClock clock(times != nullptr, st);
+  return prove_core(chip, evals, n, ch, opt, times ? times : &local, clock);
+}
+
+namespace {
+// The prover from device evaluations (evals, n) in the library layout (column-major,
+// bit-reversed): everything after the fronts.  The inputs have been checked.
+std::vector<uint8_t> prove_core(int chip, const uint32_t* evals, size_t n, Challenger& ch_io,
+                                const UniOptions& opt, StageTimes* tms, StageClock& clock) {
+  int K = 0, degree = 0, lqd = 0;
+  uni_air_shape_or_throw(chip, &K, &degree, &lqd);
+  const int w = CHIP_INFO[chip].main_w;
   const int logn = log2i(n), Lmax = logn + LOG_BLOWUP;
   const size_t N = 2 * n;
   const int nchunks = 1 << lqd;
-
   hipStream_t st = stream();
-  struct Rewind {  // the pinned upload arena is rewound when the call is done (as ProofScope)
-    hipStream_t st;
-    ~Rewind() {
-      (void)hipStreamSynchronize(st);
-      staging_reset();
-    }
-  } rewind{st};
   Challenger ch = ch_io;
-  StageTimes local;
-  StageTimes* tms = times ? times : &local;
-  StageClock clock(times != nullptr, st);
 
   // ---- trace commit (Pcs::commit of one matrix on H_n)
-  DBuf<uint32_t> evals(n * (size_t)w);
-  {
-    DBuf<uint32_t> rm(n * (size_t)w);
-    upload_bulk(rm.p, trace, n * (size_t)w * 4, st);
-    // KoalaBear words are Montgomery residues < p; a larger word breaks mmul's b < p bound
-    if (count_noncanonical(rm.p, n * (size_t)w, st))
-      throw std::runtime_error(std::string("uni_stark: non-canonical field word (>= p) in ") +
-                               CHIP_INFO[chip].name);
-    transpose_bitrev(rm.p, n, w, evals.p, st);
-  }
   Round tracer;
   tracer.mats.resize(1);
-  commit_lde(tracer.mats[0], evals.p, n, w, ONE, st);
+  commit_lde(tracer.mats[0], evals, n, w, ONE, st);
   tracer.commit(st, /*fetch_root=*/true);
   clock.stage(&tms->main_commit);
 
@@ -508,5 +547,6 @@ std::vector<uint8_t> uni_prove(int chip, const uint32_t* trace, size_t height, s
   ch_io = ch;
   return out;
 }
+}  // namespace
 
 }  // namespace bfz

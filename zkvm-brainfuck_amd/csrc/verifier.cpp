@@ -495,8 +495,8 @@ VerifyOutcome run_host(const std::string& src, const uint32_t vk_commit[8], cons
 // ------------------------------------------------------------------ packing for the device
 // The per-query shape checks of check_query, in its order; false at the first that would throw.
 bool query_shape_ok(const ShardState& S, const QueryProof& qp) {
-  if (qp.inputs.size() != 4) return false;
-  for (int rr = 0; rr < 4; rr++) {
+  if (qp.inputs.size() != (size_t)S.nrounds) return false;
+  for (int rr = 0; rr < S.nrounds; rr++) {
     const BatchOpening& bo = qp.inputs[rr];
     if (bo.rows.size() != S.rounds[rr].size()) return false;
     int lbmax = 0;
@@ -528,7 +528,9 @@ void pack_proof(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* fir
   D.nq = nq;
   D.log_max = (uint32_t)S.log_max;
   D.ncommit = S.ncommit;
+  D.nrounds = (uint32_t)S.nrounds;
   D.final_poly = S.final_poly;
+  if (S.nrounds < 1 || S.nrounds > 4) throw std::runtime_error("verify_batch: bad round count");
   if (S.log_max < 1 || S.log_max > 24) throw std::runtime_error("verify_batch: log height out of range");
   std::vector<uint32_t>& W = B.words;
 
@@ -536,7 +538,7 @@ void pack_proof(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* fir
   uint32_t rec = 0;
   std::vector<int> ord[4];                  // Merkle order of each round's matrices
   std::vector<uint32_t> mat_off[4];         // record offset of matrix i's row
-  for (int rr = 0; rr < 4; rr++) {
+  for (int rr = 0; rr < S.nrounds; rr++) {
     const std::vector<VMat>& ms = S.rounds[rr];
     ord[rr].resize(ms.size());
     for (size_t i = 0; i < ms.size(); i++) ord[rr][i] = (int)i;
@@ -571,7 +573,7 @@ void pack_proof(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* fir
   // reduced openings: per LDE height, the matrices in the verifier's order (round, then matrix),
   // alpha^k running over (matrix, point, column) across the rounds
   std::vector<int> heights;
-  for (int rr = 0; rr < 4; rr++)
+  for (int rr = 0; rr < S.nrounds; rr++)
     for (const VMat& m : S.rounds[rr]) {
       const int lh = m.log_n + LOG_BLOWUP;
       if (std::find(heights.begin(), heights.end(), lh) == heights.end()) heights.push_back(lh);
@@ -586,7 +588,7 @@ void pack_proof(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* fir
     H.z0 = S.zeta;
     H.z1 = ef_mul_base(S.zeta, two_adic_gen(heights[j] - LOG_BLOWUP));
     EF apow = ef_one();
-    for (int rr = 0; rr < 4; rr++)
+    for (int rr = 0; rr < S.nrounds; rr++)
       for (size_t i = 0; i < S.rounds[rr].size(); i++) {
         const VMat& m = S.rounds[rr][i];
         if (m.log_n + LOG_BLOWUP != heights[j]) continue;
@@ -626,7 +628,7 @@ void pack_proof(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* fir
   D.qbase = (uint32_t)W.size();
   for (uint32_t q = 0; q < nq; q++) {
     const QueryProof& qp = pf.queries[q];
-    for (int rr = 0; rr < 4; rr++) {
+    for (int rr = 0; rr < S.nrounds; rr++) {
       const BatchOpening& bo = qp.inputs[rr];
       for (int i : ord[rr]) W.insert(W.end(), bo.rows[i].begin(), bo.rows[i].end());
       for (const Digest& d : bo.path) W.insert(W.end(), d.begin(), d.end());
@@ -645,6 +647,7 @@ void pack_proof(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* fir
   B.ro_words += (size_t)nq * VQ_RO_SLOTS * 4;
   B.max_nq = std::max(B.max_nq, nq);
   B.max_ncommit = std::max(B.max_ncommit, S.ncommit);
+  B.max_nrounds = std::max(B.max_nrounds, (uint32_t)S.nrounds);
   std::memcpy(&W[B.desc_off() + (size_t)slot * (sizeof(VProof) / 4)], &D, sizeof D);
 }
 
@@ -675,46 +678,28 @@ bool verify_shard(const std::string& src, const uint32_t vk_commit[8], const Sha
   return o.ok;
 }
 
-std::vector<VerifyOutcome> verify_batch(const std::string& src, const uint32_t vk_commit[8],
-                                        const uint8_t* const* proofs, const size_t* lens, size_t n,
-                                        const VerifyOptions& opt, QueryRunner run_queries) {
+namespace {
+// The device path of a batch, for any proof kind whose query loop is check_query over a
+// ShardState: Slot holds one decoded proof and its state `S`; stage(i, slot) decodes proof i and
+// runs everything before the query loop (throwing the reason of the first failed check),
+// after(i, slot) runs what follows the loop.  The query loops of the proofs that got through
+// stage are packed into one QueryBatch per chunk and handed to run_queries.
+template <class Slot, class Stage, class After>
+std::vector<VerifyOutcome> batch_on_device(const size_t* lens, size_t n, QueryRunner run_queries,
+                                           Stage stage, After after) {
   std::vector<VerifyOutcome> out(n);
-  if (!run_queries) {  // one proof decoded at a time, as bfz_verify
-    for (size_t i = 0; i < n; i++) {
-      try {
-        const ShardProof pf = decode_bfz1(proofs[i], lens[i]);
-        out[i] = run_host(src, vk_commit, pf, opt);
-      } catch (const std::exception& e) {
-        out[i].why = e.what();
-      }
-    }
-    return out;
-  }
   // the device pass takes the proofs in chunks that bound the packed batch (2^31 words at most)
   constexpr size_t CHUNK_PROOFS = 1024, CHUNK_BYTES = (size_t)512 << 20;
   for (size_t i0 = 0; i0 < n;) {
     size_t i1 = i0, bytes = 0;
     while (i1 < n && i1 - i0 < CHUNK_PROOFS && (i1 == i0 || bytes + lens[i1] <= CHUNK_BYTES)) bytes += lens[i1++];
     const size_t k = i1 - i0;
-    std::vector<ShardProof> pfs(k);
-    std::vector<bool> decoded(k, false);
-    for (size_t j = 0; j < k; j++) {
-      try {
-        pfs[j] = decode_bfz1(proofs[i0 + j], lens[i0 + j]);
-        decoded[j] = true;
-      } catch (const std::exception& e) {
-        out[i0 + j].why = e.what();
-      }
-    }
     // stage one on the host; the survivors are packed
-    std::vector<ShardState> st(k);
-    std::vector<int> slot_of(k, -1);
+    std::vector<Slot> slots(k);
     std::vector<size_t> packed;
     for (size_t j = 0; j < k; j++) {
-      if (!decoded[j]) continue;
       try {
-        before_queries(src, vk_commit, pfs[j], opt, st[j]);
-        slot_of[j] = (int)packed.size();
+        stage(i0 + j, slots[j]);
         packed.push_back(j);
       } catch (const std::exception& e) {
         out[i0 + j].why = e.what();
@@ -735,14 +720,15 @@ std::vector<VerifyOutcome> verify_batch(const std::string& src, const uint32_t v
       // such as a preprocessed chip whose claimed log degree is not its key's: more heights than
       // the descriptor holds) is that proof's matter, not the call's: its slot stays empty and
       // all its queries run on the host below, so it gets the host's reason.
-      const uint32_t max_nq = B.max_nq, max_ncommit = B.max_ncommit;
+      const uint32_t max_nq = B.max_nq, max_ncommit = B.max_ncommit, max_nrounds = B.max_nrounds;
       const size_t words = B.words.size(), leaf_words = B.leaf_words, ro_words = B.ro_words;
       try {
-        pack_proof(st[packed[s]], B, s, &first_bad[s]);
+        pack_proof(slots[packed[s]].S, B, s, &first_bad[s]);
       } catch (const std::exception&) {
         B.words.resize(words);
         B.max_nq = max_nq;
         B.max_ncommit = max_ncommit;
+        B.max_nrounds = max_nrounds;
         B.leaf_words = leaf_words;
         B.ro_words = ro_words;
         std::fill_n(&B.words[B.desc_off() + (size_t)s * (sizeof(VProof) / 4)], sizeof(VProof) / 4, 0u);
@@ -754,7 +740,7 @@ std::vector<VerifyOutcome> verify_batch(const std::string& src, const uint32_t v
     for (uint32_t s = 0; s < B.nproofs; s++) {
       const size_t j = packed[s];
       VerifyOutcome& o = out[i0 + j];
-      const ShardState& S = st[j];
+      const ShardState& S = slots[j].S;
       if (keys[s] != VQ_NO_FAILURE) {  // the first failure among the packed queries
         if ((keys[s] >> 6) >= first_bad[s]) throw std::runtime_error("verify_batch: device key out of range");
         o.query = (int)(keys[s] >> 6);
@@ -768,7 +754,7 @@ std::vector<VerifyOutcome> verify_batch(const std::string& src, const uint32_t v
           check_query(S, q);
         }
         o.query = -1;
-        after_queries(S);
+        after(i0 + j, slots[j]);
         o.ok = true;
       } catch (const std::exception& e) {
         o.why = e.what();
@@ -777,6 +763,36 @@ std::vector<VerifyOutcome> verify_batch(const std::string& src, const uint32_t v
     i0 = i1;
   }
   return out;
+}
+
+}  // namespace
+
+std::vector<VerifyOutcome> verify_batch(const std::string& src, const uint32_t vk_commit[8],
+                                        const uint8_t* const* proofs, const size_t* lens, size_t n,
+                                        const VerifyOptions& opt, QueryRunner run_queries) {
+  if (!run_queries) {  // one proof decoded at a time, as bfz_verify
+    std::vector<VerifyOutcome> out(n);
+    for (size_t i = 0; i < n; i++) {
+      try {
+        const ShardProof pf = decode_bfz1(proofs[i], lens[i]);
+        out[i] = run_host(src, vk_commit, pf, opt);
+      } catch (const std::exception& e) {
+        out[i].why = e.what();
+      }
+    }
+    return out;
+  }
+  struct Slot {
+    ShardProof pf;
+    ShardState S;
+  };
+  return batch_on_device<Slot>(
+      lens, n, run_queries,
+      [&](size_t i, Slot& s) {
+        s.pf = decode_bfz1(proofs[i], lens[i]);
+        before_queries(src, vk_commit, s.pf, opt, s.S);
+      },
+      [](size_t, const Slot& s) { after_queries(s.S); });
 }
 
 // ------------------------------------------------------------------ per-chip uni-STARK proofs
@@ -804,80 +820,121 @@ EF fold_air_any(int chip, const std::vector<EF>& ml, const std::vector<EF>& mn, 
 }
 }  // namespace
 
-// p3_uni_stark::verify [p3-recalled] as utils::uni_stark_verify calls it (utils/prove.rs:129-159):
-// shapes from the chip table (never from the proof), the transcript replay, PCS verify, the
-// quotient recomposed at zeta from its chunks, the selectors at zeta, the AIR folded with alpha.
+// p3_uni_stark::verify [p3-recalled] as utils::uni_stark_verify calls it (utils/prove.rs:129-159),
+// in verify_shard's three stages: uni_before_queries (decode, shapes from the chip table, never
+// from the proof, the transcript head, pcs_transcript), check_query over S with two input rounds,
+// uni_after_queries (the quotient recomposed at zeta from its chunks, the selectors at zeta, the
+// AIR folded with alpha).  S refers into u: a UniState stays where it was filled.
+namespace {
+struct UniState {
+  UniProof u;
+  ShardState S;
+  int chip = -1, log_n = 0, nchunks = 0;
+  EF alpha;
+  std::vector<uint32_t> sh;  // chunk j's domain shift
+};
+
+void uni_before_queries(int chip, Challenger& ch, const uint8_t* proof, size_t len,
+                        const UniOptions& opt, UniState& U) {
+  int K = 0, degree = 0, lqd = 0;
+  if (!uni_air_shape(chip, &K, &degree, &lqd) || lqd > 1)
+    throw std::runtime_error("chip has no uni-STARK AIR");
+  U.u = decode_bfu1(proof, len);
+  const UniProof& u = U.u;
+  if ((int)u.chip != chip) throw std::runtime_error("proof is for another chip");
+  // unsigned: a huge word must not become a negative shift count below
+  if (u.log_degree > 23) throw std::runtime_error("log degree out of range");
+  const int log_n = U.log_n = (int)u.log_degree, nchunks = U.nchunks = 1 << lqd;
+  U.chip = chip;
+  const size_t w = (size_t)CHIP_INFO[chip].main_w;
+  if (u.trace_local.size() != w || u.trace_next.size() != w || u.chunks.size() != (size_t)nchunks)
+    throw std::runtime_error("opened-value shape mismatch");
+  for (const std::vector<EF>& c : u.chunks)
+    if (c.size() != 4) throw std::runtime_error("opened-value shape mismatch");
+
+  // ---- transcript head (U1, U2)
+  if (opt.observe_degree) ch.observe(to_mont((uint32_t)log_n));
+  ch.observe_digest(u.pcs.main_root.data());
+  U.alpha = ch.sample_ef();
+  ch.observe_digest(u.pcs.quot_root.data());
+  const EF zeta = ch.sample_ef();
+
+  // ---- PCS verify: [trace: (zeta, zeta w_n)], [chunk j: (zeta)] on 3 w_(n 2^lqd)^j H_n
+  ShardState& S = U.S;
+  S.pf = &u.pcs;
+  S.nrounds = 2;
+  S.zeta = zeta;
+  S.roots[0] = u.pcs.main_root.data();
+  S.roots[1] = u.pcs.quot_root.data();
+  S.rounds[0].push_back(VMat{log_n, ONE, (int)w, 2, {zeta, ef_mul_base(zeta, two_adic_gen(log_n))},
+                             {&u.trace_local, &u.trace_next}});
+  const uint32_t wq = two_adic_gen(log_n + lqd);
+  U.sh.resize(nchunks);
+  for (int j = 0; j < nchunks; j++) {
+    U.sh[j] = mmul(to_mont(3), mpow(wq, (uint64_t)j));
+    S.rounds[1].push_back(VMat{log_n, U.sh[j], 4, 1, {zeta, zeta}, {&u.chunks[j], &u.chunks[j]}});
+  }
+  pcs_transcript(S, ch, opt.observe_openings, opt.num_queries);
+}
+
+// The quotient at zeta from its chunks, the selectors, the folded constraints.
+void uni_after_queries(const UniState& U) {
+  const UniProof& u = U.u;
+  const int log_n = U.log_n, nchunks = U.nchunks, chip = U.chip;
+  const std::vector<uint32_t>& sh = U.sh;
+  const EF zeta = U.S.zeta;
+  EF quot = ef_zero();
+  for (int a = 0; a < nchunks; a++) {
+    EF zps = ef_one();
+    for (int b = 0; b < nchunks; b++)
+      if (b != a)
+        zps = ef_mul(zps, ef_mul(zp_at(log_n, sh[b], zeta), ef_inv(zp_at(log_n, sh[b], ef_base(sh[a])))));
+    for (int e = 0; e < 4; e++) quot = ef_add(quot, ef_mul(ef_mul(zps, monomial(e)), u.chunks[a][e]));
+  }
+  const uint32_t gn_inv = minv(two_adic_gen(log_n));
+  EF zh = zeta;
+  for (int k = 0; k < log_n; k++) zh = ef_mul(zh, zh);
+  zh = ef_sub(zh, ef_one());
+  const EF first = ef_mul(zh, ef_inv(ef_sub(zeta, ef_one())));
+  const EF last = ef_mul(zh, ef_inv(ef_sub(zeta, ef_base(gn_inv))));
+  const EF trans = ef_sub(zeta, ef_base(gn_inv));
+  const EF folded = fold_air_any(chip, u.trace_local, u.trace_next, first, last, trans, U.alpha);
+  if (!ef_eq(ef_mul(folded, ef_inv(zh)), quot))
+    throw std::runtime_error(std::string("OOD evaluation mismatch on chip ") + CHIP_INFO[chip].name);
+}
+}  // namespace
+
 VerifyOutcome uni_verify(int chip, Challenger& ch, const uint8_t* proof, size_t len,
                          const UniOptions& opt) {
   VerifyOutcome o;
   try {
-    int K = 0, degree = 0, lqd = 0;
-    if (!uni_air_shape(chip, &K, &degree, &lqd) || lqd > 1)
-      throw std::runtime_error("chip has no uni-STARK AIR");
-    const UniProof u = decode_bfu1(proof, len);
-    if ((int)u.chip != chip) throw std::runtime_error("proof is for another chip");
-    // unsigned: a huge word must not become a negative shift count below
-    if (u.log_degree > 23) throw std::runtime_error("log degree out of range");
-    const int log_n = (int)u.log_degree, nchunks = 1 << lqd;
-    const size_t w = (size_t)CHIP_INFO[chip].main_w;
-    if (u.trace_local.size() != w || u.trace_next.size() != w || u.chunks.size() != (size_t)nchunks)
-      throw std::runtime_error("opened-value shape mismatch");
-    for (const std::vector<EF>& c : u.chunks)
-      if (c.size() != 4) throw std::runtime_error("opened-value shape mismatch");
-
-    // ---- transcript head (U1, U2)
-    if (opt.observe_degree) ch.observe(to_mont((uint32_t)log_n));
-    ch.observe_digest(u.pcs.main_root.data());
-    const EF alpha = ch.sample_ef();
-    ch.observe_digest(u.pcs.quot_root.data());
-    const EF zeta = ch.sample_ef();
-
-    // ---- PCS verify: [trace: (zeta, zeta w_n)], [chunk j: (zeta)] on 3 w_(n 2^lqd)^j H_n
-    ShardState S;
-    S.pf = &u.pcs;
-    S.nrounds = 2;
-    S.zeta = zeta;
-    S.roots[0] = u.pcs.main_root.data();
-    S.roots[1] = u.pcs.quot_root.data();
-    S.rounds[0].push_back(VMat{log_n, ONE, (int)w, 2, {zeta, ef_mul_base(zeta, two_adic_gen(log_n))},
-                               {&u.trace_local, &u.trace_next}});
-    const uint32_t wq = two_adic_gen(log_n + lqd);
-    std::vector<uint32_t> sh(nchunks);
-    for (int j = 0; j < nchunks; j++) {
-      sh[j] = mmul(to_mont(3), mpow(wq, (uint64_t)j));
-      S.rounds[1].push_back(VMat{log_n, sh[j], 4, 1, {zeta, zeta}, {&u.chunks[j], &u.chunks[j]}});
-    }
-    pcs_transcript(S, ch, opt.observe_openings, opt.num_queries);
-    for (uint32_t q = 0; q < S.nq; q++) {
+    UniState U;
+    uni_before_queries(chip, ch, proof, len, opt, U);
+    for (uint32_t q = 0; q < U.S.nq; q++) {
       o.query = (int)q;
-      check_query(S, q);
+      check_query(U.S, q);
     }
     o.query = -1;
-
-    // ---- the quotient at zeta from its chunks, the selectors, the folded constraints
-    EF quot = ef_zero();
-    for (int a = 0; a < nchunks; a++) {
-      EF zps = ef_one();
-      for (int b = 0; b < nchunks; b++)
-        if (b != a)
-          zps = ef_mul(zps, ef_mul(zp_at(log_n, sh[b], zeta), ef_inv(zp_at(log_n, sh[b], ef_base(sh[a])))));
-      for (int e = 0; e < 4; e++) quot = ef_add(quot, ef_mul(ef_mul(zps, monomial(e)), u.chunks[a][e]));
-    }
-    const uint32_t gn_inv = minv(two_adic_gen(log_n));
-    EF zh = zeta;
-    for (int k = 0; k < log_n; k++) zh = ef_mul(zh, zh);
-    zh = ef_sub(zh, ef_one());
-    const EF first = ef_mul(zh, ef_inv(ef_sub(zeta, ef_one())));
-    const EF last = ef_mul(zh, ef_inv(ef_sub(zeta, ef_base(gn_inv))));
-    const EF trans = ef_sub(zeta, ef_base(gn_inv));
-    const EF folded = fold_air_any(chip, u.trace_local, u.trace_next, first, last, trans, alpha);
-    if (!ef_eq(ef_mul(folded, ef_inv(zh)), quot))
-      throw std::runtime_error(std::string("OOD evaluation mismatch on chip ") + CHIP_INFO[chip].name);
+    uni_after_queries(U);
     o.ok = true;
   } catch (const std::exception& e) {
     o.why = e.what();
   }
   return o;
+}
+
+std::vector<VerifyOutcome> uni_verify_batch(const int* chips, Challenger* chs,
+                                            const uint8_t* const* proofs, const size_t* lens,
+                                            size_t n, const UniOptions& opt, QueryRunner run_queries) {
+  if (!run_queries) {
+    std::vector<VerifyOutcome> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = uni_verify(chips[i], chs[i], proofs[i], lens[i], opt);
+    return out;
+  }
+  return batch_on_device<UniState>(
+      lens, n, run_queries,
+      [&](size_t i, UniState& U) { uni_before_queries(chips[i], chs[i], proofs[i], lens[i], opt, U); },
+      [](size_t, const UniState& U) { uni_after_queries(U); });
 }
 
 // Columns a chip's constraints read at the next row (quotient.rs:41-42), found by perturbing

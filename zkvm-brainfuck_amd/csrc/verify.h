@@ -2,15 +2,15 @@
 // (verifier.cpp pack_proof) and the entry point that runs it.
 //
 // The verifier's query loop (TwoAdicFriPcs::verify + fri::verifier [p3-recalled], the host form is
-// verifier.cpp check_query) is, per query, four MerkleTreeMmcs openings of the input rounds, the
-// reduced openings of every LDE height, the FRI fold chain and one Merkle opening per commit-phase
-// step.  Everything a kernel indexes with -- widths, heights, path lengths, offsets -- is written
+// verifier.cpp check_query) is, per query, one MerkleTreeMmcs opening per input round (four in a
+// machine proof, two in a per-chip uni-STARK proof), the reduced openings of every LDE height, the
+// FRI fold chain and one Merkle opening per commit-phase step.  Everything a kernel indexes with -- widths, heights, path lengths, offsets -- is written
 // into the descriptors below by the host from the program, the vk and the shapes it has already
 // validated; the proof's own bytes are only ever read as field words at those offsets.
 //
 // One batch is one array of 32-bit words:
 //   [0, np)            one key per proof, 0xffffffff on upload; the kernels atomicMin the key
-//                      query * 64 + stage of every failed check into it (stage: 0..3 the input
+//                      query * 64 + stage of every failed check into it (stage: 0..nrounds-1 the input
 //                      rounds, 4 + s commit-phase step s, 63 the final-value comparison), so the
 //                      smallest key is the first failure in the host verifier's order
 //   [np, np + 64)      two_adic_gen(k) and its inverse, k < 32
@@ -63,6 +63,7 @@ struct VProof {
   uint32_t leaf_base;           // words into the leaves workspace: 8 * ncommit per query
   uint32_t ro_base;             // words into the reduced-openings workspace: 4 * VQ_RO_SLOTS per query
   uint32_t nheights, nmats;
+  uint32_t nrounds;             // input rounds in use: 4 in a machine proof, 2 in a BFU1 proof
   kb::EF final_poly;
   VRoundD rd[4];
   VHeightD hs[VQ_MAX_HEIGHTS];
@@ -73,7 +74,7 @@ static_assert(sizeof(VProof) % 4 == 0, "VProof is an array of words");
 struct QueryBatch {
   std::vector<uint32_t> words;  // the layout above
   uint32_t nproofs = 0;
-  uint32_t max_nq = 0, max_ncommit = 0;
+  uint32_t max_nq = 0, max_ncommit = 0, max_nrounds = 0;
   size_t leaf_words = 0, ro_words = 0;  // workspace sizes
   size_t desc_off() const { return (size_t)nproofs + 64; }
 };

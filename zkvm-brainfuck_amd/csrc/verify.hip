@@ -57,8 +57,9 @@ __global__ __launch_bounds__(256) void k_verify_inputs(uint32_t* __restrict__ B,
   const VProof* __restrict__ D = reinterpret_cast<const VProof*>(B + np + 64) + proof;
   const uint32_t job = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
   const int lane = threadIdx.x & 15;
-  if (job >= D->nq * 4) return;
-  const uint32_t q = job >> 2, rr = job & 3;
+  const uint32_t nr = D->nrounds;  // 4 (machine proof) or 2 (BFU1); 0 in an empty slot
+  if (job >= D->nq * nr) return;
+  const uint32_t q = job / nr, rr = job - q * nr;
   const LaneConsts kc = lane_consts(lane);
   const VRoundD* __restrict__ R = &D->rd[rr];
   const uint32_t* __restrict__ rec = B + D->qbase + (size_t)q * D->qstride;
@@ -199,8 +200,8 @@ void verify_queries_device(const QueryBatch& b, uint32_t* keys, hipStream_t st) 
                        dim3(256), 0, st, d.p, np, leaves.p);
     KCHECK();
   }
-  hipLaunchKernelGGL(k_verify_inputs, dim3(ceil_div((size_t)b.max_nq * 4 * 16, 256), np), dim3(256), 0,
-                     st, d.p, np);
+  hipLaunchKernelGGL(k_verify_inputs, dim3(ceil_div((size_t)b.max_nq * b.max_nrounds * 16, 256), np),
+                     dim3(256), 0, st, d.p, np);
   KCHECK();
   HIP_CHECK(hipMemcpyAsync(keys, d.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
