@@ -11,6 +11,7 @@
 //! | `open` (prover.rs:242-553)                      | `bfz_open` + `bfz_proof_to_bincode`          |
 //! | `prove` (prover.rs:560-582)                     | `bfz_record_from_events` + record commit + open |
 //! | `debug_constraints` (prover.rs:139-149)         | `bfz_record_debug_constraints` (device traces) |
+//! | `utils::uni_stark_prove` of a new `A: Air` (utils/prove.rs:97-159) | `bfz_air_prove` / `bfz_air_verify` on a BFA1 program |
 //!
 //! `prove` overrides the default: instead of `generate_dependencies` + `generate_traces` on the
 //! host and a 1 GB trace upload, the record's event vectors (~50 B per cycle) go to the device,

@@ -270,6 +270,23 @@ pub struct bfz_verify_outcome {
     pub why: [c_char; 120],
 }
 
+/// The shape of a constraint program and the size of its compiled list (`bfz_air_info`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bfz_air_shape {
+    pub width: i32,
+    pub num_nodes: i32,
+    pub num_constraints: i32,
+    pub degree: i32,
+    pub log_quotient_degree: i32,
+    pub instructions: i32,
+    pub live_values: i32,
+    pub _pad: i32,
+}
+
+/// Chip word of a BFU1 proof made from a constraint program (`bfz_air_prove`).
+pub const BFZ_AIR_CHIP: u32 = 0xffff_ffff;
+
 /// The AIR-only row check of one chip (`bfz_uni_check`): what `p3_uni_stark::prove` checks in a
 /// debug build (crates/core/machine/src/utils/prove.rs:97-112).
 #[repr(C)]
@@ -423,6 +440,22 @@ extern "C" {
     pub fn bfz_uni_verify_batch(chips: *const c_int, chs: *mut bfz_challenger,
                                 proofs: *const *const u8, lens: *const usize, n: usize,
                                 on_device: c_int, out: *mut bfz_verify_outcome) -> c_int;
+
+    /// Caller-defined AIRs as BFA1 constraint programs: `uni_stark_prove` / `uni_stark_verify`
+    /// are generic over `A: Air` (crates/core/machine/src/utils/prove.rs:97-159).
+    pub fn bfz_air_export(chip: c_int, prog: *mut *mut u8, len: *mut usize) -> c_int;
+    pub fn bfz_air_info(prog: *const u8, len: usize, out: *mut bfz_air_shape) -> c_int;
+    pub fn bfz_air_eval(prog: *const u8, len: usize, local: *const u32, next: *const u32,
+                        is_first: *const u32, is_last: *const u32, is_transition: *const u32,
+                        out: *mut u32) -> c_int;
+    pub fn bfz_air_check(prog: *const u8, len: usize, trace: *const u32, height: usize,
+                         width: usize, on_device: c_int, out: *mut bfz_uni_check_result,
+                         first_fail_per_row: *mut i32) -> c_int;
+    pub fn bfz_air_prove(prog: *const u8, len: usize, trace: *const u32, height: usize,
+                         width: usize, ch: *mut bfz_challenger, proof: *mut *mut u8,
+                         proof_len: *mut usize, timings: *mut bfz_timings) -> c_int;
+    pub fn bfz_air_verify(prog: *const u8, len: usize, ch: *mut bfz_challenger, proof: *const u8,
+                          proof_len: usize, out: *mut bfz_verify_outcome) -> c_int;
 
     pub fn bfz_set_num_queries(num_queries: c_int) -> c_int;
     pub fn bfz_set_pcs_variant(observe_openings: c_int) -> c_int;

@@ -655,6 +655,70 @@ int bfz_record_uni_prove(const bfz_record* rec, int chip, bfz_challenger* ch,
 int bfz_uni_verify_batch(const int* chips, bfz_challenger* chs, const uint8_t* const* proofs,
                          const size_t* lens, size_t n, int on_device, bfz_verify_outcome* out);
 
+/* ---- Caller-defined AIRs as constraint programs ----
+ * utils::uni_stark_prove / uni_stark_verify are generic over A: Air
+ * (crates/core/machine/src/utils/prove.rs:97-159); the bfz_uni_* calls above take the five chips
+ * compiled into the library.  Here the AIR arrives as data, so a new chip, or one changed
+ * constraint, is proven, row-checked and verified without rebuilding the library.  As above,
+ * send / receive are no-ops (air/builder.rs:232-239,273-275): no preprocessed columns, no public
+ * values, no extension-field columns.
+ *
+ * The program format "BFA1": little-endian u32 words, field constants as Montgomery words.
+ *     "BFA1" | width | n_nodes | n_constraints
+ *     n_nodes x (op, a, b)
+ *     n_constraints x node index          -- emission order (acc = acc * alpha + c)
+ *   op 0 CONST (a = a word < p), 1 LOCAL (a = column), 2 NEXT (a = column), 3 IS_FIRST_ROW,
+ *   4 IS_LAST_ROW, 5 IS_TRANSITION, 6 ADD, 7 SUB, 8 MUL, 9 NEG (a only).  Unused operands are 0;
+ *   the operands of ops 6-9 are indices of EARLIER nodes (p3's SymbolicExpression [p3-recalled]
+ *   written flat, already in topological order).
+ * A constraint's degree follows SymbolicExpression::degree_multiple: a trace variable 1, a
+ * constant 0, is_first_row / is_last_row 1, is_transition 0, add / sub the maximum, mul the sum,
+ * neg the identity; the AIR's degree is the maximum, log_quotient_degree = log2_ceil(degree - 1).
+ * Every call validates the program first (a malformed one: negative status, the message names the
+ * word offset) and refuses a degree above 3 and a program whose compiled instruction list keeps
+ * more than BFZ_AIR_MAX_LIVE values live at once (the message names the count).
+ *
+ *   bfz_air_export  host only: the BFA1 program of a built-in chip's AIR (the chips of
+ *                   bfz_uni_info, the same refusals); *prog is freed with bfz_free.  Proofs and
+ *                   checks made from it equal the compiled chip's byte for byte.
+ *   bfz_air_info    host only: validates, and reports the shape and the compiled list's size.
+ *   bfz_air_eval    host only: the K constraint values over extension-field rows.  local / next:
+ *                   width x 4 Montgomery words; the selectors 4 words each; out: K x 4.
+ *   bfz_air_check   bfz_uni_check for a program: out->chip = -1; first_fail_per_row optional,
+ *                   natural order.
+ *   bfz_air_prove   bfz_uni_prove's contract: the same refusals for height, width and words >= p,
+ *                   ch is advanced, a trace that violates the AIR still proves, and it honours
+ *                   bfz_set_num_queries, bfz_set_pcs_variant and BFZ_UNI_OBSERVE_DEGREE.  The proof
+ *                   is BFU1 with the chip word BFZ_AIR_CHIP, a label outside the transcript.  Like
+ *                   p3_uni_stark, the AIR itself is NOT bound into the transcript: a verifier must
+ *                   know which program a proof is for.
+ *   bfz_air_verify  bfz_uni_verify's contract; returns 0 whenever the check RAN.  The AIR is the
+ *                   caller's program, so the proof's chip word is not interpreted, and the chip
+ *                   name in a reason reads "custom" ("OOD evaluation mismatch on chip custom").
+ * bfz_uni_verify rejects a BFZ_AIR_CHIP proof with "proof is for another chip". */
+#define BFZ_AIR_MAX_WIDTH 64        /* the library's column maps are 64 wide */
+#define BFZ_AIR_MAX_NODES 4096
+#define BFZ_AIR_MAX_CONSTRAINTS 512
+#define BFZ_AIR_MAX_LIVE 32         /* the interpreter's slot count */
+#define BFZ_AIR_CHIP 0xffffffffu    /* chip word of a BFU1 proof made from a program */
+typedef struct {
+  int32_t width, num_nodes, num_constraints, degree, log_quotient_degree;
+  int32_t instructions, live_values, _pad;   /* of the compiled list */
+} bfz_air_shape;
+int bfz_air_export(int chip, uint8_t** prog, size_t* len);
+int bfz_air_info(const uint8_t* prog, size_t len, bfz_air_shape* out);
+int bfz_air_eval(const uint8_t* prog, size_t len, const uint32_t* local, const uint32_t* next,
+                 const uint32_t is_first[4], const uint32_t is_last[4],
+                 const uint32_t is_transition[4], uint32_t* out);
+int bfz_air_check(const uint8_t* prog, size_t len, const uint32_t* trace, size_t height,
+                  size_t width, int on_device, bfz_uni_check_result* out,
+                  int32_t* first_fail_per_row);
+int bfz_air_prove(const uint8_t* prog, size_t len, const uint32_t* trace, size_t height,
+                  size_t width, bfz_challenger* ch, uint8_t** proof, size_t* proof_len,
+                  bfz_timings* timings);
+int bfz_air_verify(const uint8_t* prog, size_t len, bfz_challenger* ch, const uint8_t* proof,
+                   size_t proof_len, bfz_verify_outcome* out);
+
 /* FRI_QUERIES (kb31_poseidon2.rs:59-62): 1..4096, or 0 = environment FRI_QUERIES / 84. */
 int bfz_set_num_queries(int num_queries);
 

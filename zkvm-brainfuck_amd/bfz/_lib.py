@@ -97,6 +97,13 @@ class UniCheckC(ctypes.Structure):
                 ("_pad", c_int32)]
 
 
+class AirShapeC(ctypes.Structure):
+    """bfz_air_shape: the shape of a constraint program and the size of its compiled list."""
+    _fields_ = [("width", c_int32), ("num_nodes", c_int32), ("num_constraints", c_int32),
+                ("degree", c_int32), ("log_quotient_degree", c_int32), ("instructions", c_int32),
+                ("live_values", c_int32), ("_pad", c_int32)]
+
+
 class VerifyOutcomeC(ctypes.Structure):
     """bfz_verify_outcome: one proof's verdict from bfz_verify_batch."""
     _fields_ = [("ok", c_int32), ("query", c_int32), ("why", ctypes.c_char * 120)]
@@ -215,6 +222,18 @@ SIGNATURES = [
                                      POINTER(c_size_t), POINTER(Timings)]),
     ("bfz_uni_verify_batch", c_int, [POINTER(c_int), POINTER(Challenger), POINTER(POINTER(c_uint8)),
                                      POINTER(c_size_t), c_size_t, c_int, POINTER(VerifyOutcomeC)]),
+    ("bfz_air_export", c_int, [c_int, POINTER(POINTER(c_uint8)), POINTER(c_size_t)]),
+    ("bfz_air_info", c_int, [POINTER(c_uint8), c_size_t, POINTER(AirShapeC)]),
+    ("bfz_air_eval", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint32), POINTER(c_uint32),
+                             POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
+                             POINTER(c_uint32)]),
+    ("bfz_air_check", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint32), c_size_t, c_size_t,
+                              c_int, POINTER(UniCheckC), POINTER(c_int32)]),
+    ("bfz_air_prove", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint32), c_size_t, c_size_t,
+                              POINTER(Challenger), POINTER(POINTER(c_uint8)), POINTER(c_size_t),
+                              POINTER(Timings)]),
+    ("bfz_air_verify", c_int, [POINTER(c_uint8), c_size_t, POINTER(Challenger), POINTER(c_uint8),
+                               c_size_t, POINTER(VerifyOutcomeC)]),
     ("bfz_set_num_queries", c_int, [c_int]),
     ("bfz_set_pcs_variant", c_int, [c_int]),
     ("bfz_set_fault_injection", c_int, [c_int]),

@@ -849,9 +849,10 @@ class UniCheckResult:
         return self.failing_rows == 0
 
     def __str__(self) -> str:
+        name = CHIPS[self.chip] if self.chip >= 0 else "custom"  # -1: a constraint program
         if not self.failing_rows:
-            return f"{CHIPS[self.chip]}: {self.height} row(s) ok"
-        return (f"{CHIPS[self.chip]}: {self.failing_rows} failing row(s); first: row {self.first_row}, "
+            return f"{name}: {self.height} row(s) ok"
+        return (f"{name}: {self.failing_rows} failing row(s); first: row {self.first_row}, "
                 f"AIR constraint {self.first_constraint} of {self.num_constraints}")
 
 
@@ -989,6 +990,222 @@ def _uni_stark_prove_record(self, pk: BfProvingKey, stdin, chips=UNI_STARK_CHIPS
 
 
 ProverClient.uni_stark_prove_record = _uni_stark_prove_record
+
+
+# ---- caller-defined AIRs as constraint programs (bfz_air_*): uni_stark_prove / uni_stark_verify
+# are generic over A: Air (crates/core/machine/src/utils/prove.rs:97-159)
+AIR_CHIP = 0xFFFFFFFF  # BFZ_AIR_CHIP: the chip word of a proof made from a program
+_AIR_MAGIC = 0x31414642  # "BFA1"
+_KB_P = 0x7F000001
+(_OP_CONST, _OP_LOCAL, _OP_NEXT, _OP_FIRST, _OP_LAST, _OP_TRANS, _OP_ADD, _OP_SUB, _OP_MUL,
+ _OP_NEG) = range(10)
+
+
+class AirExpr:
+    """A node of an AirBuilder's program.  + - * and unary - append nodes; Python ints become
+    constants."""
+    __slots__ = ("builder", "node")
+
+    def __init__(self, builder, node):
+        self.builder, self.node = builder, node
+
+    def _bin(self, op, other, swap=False):
+        o = self.builder._lift(other)
+        a, b = (o, self) if swap else (self, o)
+        return self.builder._push(op, a.node, b.node)
+
+    def __add__(self, o):
+        return self._bin(_OP_ADD, o)
+
+    def __radd__(self, o):
+        return self._bin(_OP_ADD, o, swap=True)
+
+    def __sub__(self, o):
+        return self._bin(_OP_SUB, o)
+
+    def __rsub__(self, o):
+        return self._bin(_OP_SUB, o, swap=True)
+
+    def __mul__(self, o):
+        return self._bin(_OP_MUL, o)
+
+    def __rmul__(self, o):
+        return self._bin(_OP_MUL, o, swap=True)
+
+    def __neg__(self):
+        return self.builder._push(_OP_NEG, self.node, 0)
+
+
+class AirBuilder:
+    """Builds a BFA1 constraint program (include/bfz.h) the way an Air::eval is written:
+    local(c) / next(c) are the row's columns, is_first_row / is_last_row / is_transition the
+    selectors, const(v) a canonical field constant; assert_zero / assert_eq emit constraints in
+    order; build() returns the bytes bfz_air_* take."""
+
+    def __init__(self, width: int):
+        self.width = int(width)
+        self._nodes: List[tuple] = []
+        self._constraints: List[int] = []
+        self._leaves: Dict[tuple, AirExpr] = {}
+
+    def _push(self, op, a, b) -> AirExpr:
+        self._nodes.append((op, a, b))
+        return AirExpr(self, len(self._nodes) - 1)
+
+    def _leaf(self, op, a=0) -> AirExpr:
+        if (op, a) not in self._leaves:
+            self._leaves[(op, a)] = self._push(op, a, 0)
+        return self._leaves[(op, a)]
+
+    def _lift(self, v) -> AirExpr:
+        if isinstance(v, AirExpr):
+            if v.builder is not self:
+                raise ValueError("AirBuilder: an expression of another builder")
+            return v
+        return self.const(v)
+
+    def _col(self, c) -> int:
+        c = int(c)
+        if not 0 <= c < self.width:
+            raise ValueError(f"AirBuilder: column {c} outside the width {self.width}")
+        return c
+
+    def local(self, c: int) -> AirExpr:
+        return self._leaf(_OP_LOCAL, self._col(c))
+
+    def next(self, c: int) -> AirExpr:
+        return self._leaf(_OP_NEXT, self._col(c))
+
+    @property
+    def is_first_row(self) -> AirExpr:
+        return self._leaf(_OP_FIRST)
+
+    @property
+    def is_last_row(self) -> AirExpr:
+        return self._leaf(_OP_LAST)
+
+    @property
+    def is_transition(self) -> AirExpr:
+        return self._leaf(_OP_TRANS)
+
+    def const(self, v: int) -> AirExpr:
+        return self._leaf(_OP_CONST, ((int(v) % _KB_P) << 32) % _KB_P)  # the Montgomery word
+
+    def assert_zero(self, e) -> None:
+        self._constraints.append(self._lift(e).node)
+
+    def assert_eq(self, a, b) -> None:
+        self.assert_zero(self._lift(a) - b)
+
+    def build(self) -> bytes:
+        import struct
+        words = [_AIR_MAGIC, self.width, len(self._nodes), len(self._constraints)]
+        for n in self._nodes:
+            words.extend(n)
+        words.extend(self._constraints)
+        return struct.pack(f"<{len(words)}I", *words)
+
+
+@dataclass
+class AirInfo:
+    """bfz_air_shape: a program's shape and the size of its compiled instruction list."""
+    width: int
+    num_nodes: int
+    num_constraints: int
+    degree: int
+    log_quotient_degree: int
+    instructions: int
+    live_values: int
+
+
+def air_export(chip: int) -> bytes:
+    """bfz_air_export (host only): the BFA1 program of a built-in chip's AIR.  Raises for Program,
+    Memory and Byte as uni_stark_info does."""
+    ptr = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    check(lib().bfz_air_export(int(chip), ctypes.byref(ptr), ctypes.byref(n)))
+    return take_bytes(ptr, n.value)
+
+
+def air_info(prog: bytes) -> AirInfo:
+    """bfz_air_info (host only): validates the program; raises BfzError naming the word offset."""
+    buf, n = u8buf(prog)
+    out = _lib.AirShapeC()
+    check(lib().bfz_air_info(buf, n, ctypes.byref(out)))
+    return AirInfo(out.width, out.num_nodes, out.num_constraints, out.degree,
+                   out.log_quotient_degree, out.instructions, out.live_values)
+
+
+def air_eval(prog: bytes, local, next, is_first, is_last, is_transition):
+    """bfz_air_eval (host only): the K constraint values over extension-field rows.  local / next:
+    (width, 4) Montgomery words, the selectors 4 words each; returns a (K, 4) uint32 array."""
+    import numpy as np
+    info = air_info(prog)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    rows = [np.ascontiguousarray(m, dtype=np.uint32) for m in (local, next)]
+    sels = [np.ascontiguousarray(v, dtype=np.uint32) for v in (is_first, is_last, is_transition)]
+    if any(m.shape != (info.width, 4) for m in rows) or any(v.shape != (4,) for v in sels):
+        raise ValueError("air_eval: rows are (width, 4) and selectors (4,) Montgomery words")
+    out = np.zeros((info.num_constraints, 4), dtype=np.uint32)
+    buf, n = u8buf(prog)
+    check(lib().bfz_air_eval(buf, n, *[a.ctypes.data_as(u32p) for a in rows + sels],
+                             out.ctypes.data_as(u32p)))
+    return out
+
+
+def air_check(prog: bytes, trace, on_device: bool = True, per_row: bool = False) -> UniCheckResult:
+    """uni_stark_check for a constraint program (bfz_air_check): chip = -1 in the result."""
+    import numpy as np
+    if on_device:
+        init()
+    m = np.ascontiguousarray(trace, dtype=np.uint32)
+    if m.ndim != 2:
+        raise ValueError("air_check: the trace must be a (height, width) matrix")
+    out = _lib.UniCheckC()
+    rows = np.zeros(m.shape[0], dtype=np.int32) if per_row else None
+    buf, n = u8buf(prog)
+    check(lib().bfz_air_check(buf, n, m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                              m.shape[0], m.shape[1], int(bool(on_device)), ctypes.byref(out),
+                              rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if per_row else None))
+    return _uni_check_result(out, rows)
+
+
+def air_prove(prog: bytes, trace, ch: Optional[Challenger] = None, check: bool = False) -> bytes:
+    """uni_stark_prove for a constraint program (bfz_air_prove): the BFU1 proof bytes, chip word
+    AIR_CHIP.  ch (fresh when None) is advanced.  check=True runs air_check first and raises
+    BfzError naming the row and constraint when a row fails; by default an invalid trace still
+    proves.  The AIR is not bound into the transcript (as in p3_uni_stark): the verifier must be
+    given the same program."""
+    import numpy as np
+    init()
+    m = np.ascontiguousarray(trace, dtype=np.uint32)
+    if m.ndim != 2:
+        raise ValueError("air_prove: the trace must be a (height, width) matrix")
+    if check:
+        _raise_if_failing(air_check(prog, m, on_device=True))
+    if ch is None:
+        ch = Challenger()
+    ptr = ctypes.POINTER(ctypes.c_uint8)()
+    plen = ctypes.c_size_t()
+    buf, n = u8buf(prog)
+    # (the parameter `check` hides the module's function here)
+    _lib.check(lib().bfz_air_prove(
+        buf, n, m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), m.shape[0], m.shape[1],
+        ctypes.byref(ch), ctypes.byref(ptr), ctypes.byref(plen), None))
+    return take_bytes(ptr, plen.value)
+
+
+def air_verify(prog: bytes, proof: bytes, ch: Optional[Challenger] = None) -> None:
+    """uni_stark_verify for a constraint program (bfz_air_verify, host only); raises BfzError with
+    the verifier's reason on rejection.  ch (fresh when None) is advanced."""
+    if ch is None:
+        ch = Challenger()
+    pbuf, pn = u8buf(prog)
+    buf, n = u8buf(proof)
+    out = _lib.VerifyOutcomeC()
+    check(lib().bfz_air_verify(pbuf, pn, ctypes.byref(ch), buf, n, ctypes.byref(out)))
+    if not out.ok:
+        raise BfzError("uni-STARK verification failed: " + out.why.decode())
 
 
 def set_num_queries(q: int) -> None:

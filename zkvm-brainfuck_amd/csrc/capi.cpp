@@ -1342,14 +1342,126 @@ int bfz_uni_check(int chip, const uint32_t* trace, size_t height, size_t width, 
     if (!on_device) {
       // mmul needs words < p, and the check compares reduced words with 0
       for (size_t i = 0; i < height * width; i++)
-        if (trace[i] >= kb::P) bfz::uni_noncanonical_throw(chip);
+        if (trace[i] >= kb::P) bfz::uni_noncanonical_throw(bfz::CHIP_INFO[chip].name);
       bfz::check_air_host(chip, trace, height, cc, first_fail_per_row);
     } else {
       hipStream_t st = bfz::stream();
-      const bfz::DBuf<uint32_t> evals = bfz::uni_upload_trace(chip, trace, height, st);
+      const bfz::DBuf<uint32_t> evals =
+          bfz::uni_upload_trace(width, bfz::CHIP_INFO[chip].name, trace, height, st);
       bfz::check_air_resident(chip, evals.p, height, cc, first_fail_per_row, st);
     }
     to_c(cc, out);
+    return 0;
+  });
+}
+
+// ---- caller-defined AIRs as constraint programs (air_program.h)
+int bfz_air_export(int chip, uint8_t** prog, size_t* len) {
+  return guarded([&] {
+    if (!prog || !len) throw std::runtime_error("null argument");
+    return emit(bfz::air_export(chip), prog, len);
+  });
+}
+
+int bfz_air_info(const uint8_t* prog, size_t len, bfz_air_shape* out) {
+  return guarded([&] {
+    if (!prog || !out) throw std::runtime_error("null argument");
+    const bfz::AirProgram p = bfz::air_compile(prog, len);
+    static_assert(sizeof(bfz_air_shape) == 32, "bfz_air_shape has no gaps");
+    std::memset(out, 0, sizeof *out);
+    out->width = p.width;
+    out->num_nodes = p.num_nodes;
+    out->num_constraints = p.num_constraints;
+    out->degree = p.degree;
+    out->log_quotient_degree = p.log_quotient_degree;
+    out->instructions = p.instructions;
+    out->live_values = p.live_values;
+    return 0;
+  });
+}
+
+int bfz_air_eval(const uint8_t* prog, size_t len, const uint32_t* local, const uint32_t* next,
+                 const uint32_t is_first[4], const uint32_t is_last[4],
+                 const uint32_t is_transition[4], uint32_t* out) {
+  return guarded([&] {
+    if (!prog || !local || !next || !is_first || !is_last || !is_transition || !out)
+      throw std::runtime_error("null argument");
+    const bfz::AirProgram p = bfz::air_compile(prog, len);
+    auto ef_at = [](const uint32_t* w) {
+      kb::EF e;
+      for (int k = 0; k < 4; k++) {
+        if (w[k] >= kb::P) throw std::runtime_error("air_eval: non-canonical field word (>= p)");
+        e.c[k] = w[k];
+      }
+      return e;
+    };
+    std::vector<kb::EF> L((size_t)p.width), N((size_t)p.width), c((size_t)p.num_constraints);
+    for (int i = 0; i < p.width; i++) {
+      L[i] = ef_at(local + 4 * i);
+      N[i] = ef_at(next + 4 * i);
+    }
+    bfz::air_eval_ef(p, L.data(), N.data(), ef_at(is_first), ef_at(is_last), ef_at(is_transition),
+                     c.data());
+    std::memcpy(out, c.data(), c.size() * sizeof(kb::EF));
+    return 0;
+  });
+}
+
+int bfz_air_check(const uint8_t* prog, size_t len, const uint32_t* trace, size_t height,
+                  size_t width, int on_device, bfz_uni_check_result* out,
+                  int32_t* first_fail_per_row) {
+  return guarded([&] {
+    if (!prog || !trace || !out) throw std::runtime_error("null argument");
+    const bfz::AirProgram p = bfz::air_compile(prog, len);
+    const bfz::UniAir air = bfz::uni_air_of_program(p);
+    bfz::uni_dims_or_throw(air, height, width);
+    bfz::ChipCheck cc;
+    if (!on_device) {
+      for (size_t i = 0; i < height * width; i++)
+        if (trace[i] >= kb::P) bfz::uni_noncanonical_throw(air.name);
+      bfz::check_air_host(air, trace, height, cc, first_fail_per_row);
+    } else {
+      hipStream_t st = bfz::stream();
+      const bfz::DBuf<uint32_t> evals = bfz::uni_upload_trace(width, air.name, trace, height, st);
+      bfz::check_air_resident(air, evals.p, height, cc, first_fail_per_row, st);
+    }
+    to_c(cc, out);
+    return 0;
+  });
+}
+
+int bfz_air_prove(const uint8_t* prog, size_t len, const uint32_t* trace, size_t height,
+                  size_t width, bfz_challenger* ch, uint8_t** proof, size_t* proof_len,
+                  bfz_timings* t) {
+  return guarded([&] {
+    if (!prog || !trace || !ch || !proof || !proof_len) throw std::runtime_error("null argument");
+    const bfz::AirProgram p = bfz::air_compile(prog, len);
+    bfz::Challenger c = from_c(ch);
+    bfz::StageTimes st;
+    bfz::UniOptions uo;
+    uni_opts(uo);
+    auto v = bfz::uni_prove(bfz::uni_air_of_program(p), trace, height, width, c, uo,
+                            t ? &st : nullptr);
+    if (t) {
+      std::memset(t, 0, sizeof *t);
+      fill_timings(st, t);
+    }
+    const int r = emit(std::move(v), proof, proof_len);
+    to_c(c, ch);  // advanced as by bfz_uni_prove
+    return r;
+  });
+}
+
+int bfz_air_verify(const uint8_t* prog, size_t len, bfz_challenger* ch, const uint8_t* proof,
+                   size_t proof_len, bfz_verify_outcome* out) {
+  return guarded([&] {
+    if (!prog || !ch || !out || (!proof && proof_len)) throw std::runtime_error("null argument");
+    const bfz::AirProgram p = bfz::air_compile(prog, len);  // a refused program is an error
+    bfz::Challenger c = from_c(ch);
+    bfz::UniOptions uo;
+    uni_opts(uo);
+    to_c(bfz::uni_verify(bfz::uni_air_of_program(p), c, proof, proof_len, uo), out);
+    to_c(c, ch);
     return 0;
   });
 }

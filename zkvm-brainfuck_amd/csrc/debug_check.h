@@ -191,6 +191,13 @@ void check_chip_device(int chip, const uint32_t* mainc, const uint32_t* prepc,
 void check_air_host(int chip, const uint32_t* main, size_t h, ChipCheck& out, int32_t* per_row);
 void check_air_resident(int chip, const uint32_t* mainc, size_t h, ChipCheck& out, int32_t* per_row,
                         hipStream_t st);
+// The same for any AIR (uni_stark.h UniAir): a built-in chip as above, or a compiled constraint
+// program run by the interpreters of air_program.h (out.chip = -1).
+struct UniAir;
+void check_air_host(const UniAir& air, const uint32_t* main, size_t h, ChipCheck& out,
+                    int32_t* per_row);
+void check_air_resident(const UniAir& air, const uint32_t* mainc, size_t h, ChipCheck& out,
+                        int32_t* per_row, hipStream_t st);
 // chip, height, K and the number of LogUp batches of a result.
 void fill_chip_header(int chip, size_t h, ChipCheck& out);
 // Fills out.{failing_rows, first_row, first_constraint} from the two downloaded words.
@@ -206,5 +213,48 @@ void lookup_balance_device(int chip, const uint32_t* mainc, const uint32_t* prep
 // table.  No LDE, no commit.
 void debug_constraints_device(const ProvingKey& pk, const DeviceTraces& dt, Challenger& ch,
                               bool force_balance, DebugReport& out);
+
+#if defined(__HIPCC__)
+// ---- the block reduction of the check kernels (debug_check.hip, air_program.hip)
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+// The block's failing rows into res: wave minimum of row * K + index and ballot popcount, block
+// minimum over the four waves, then one atomicMin / atomicAdd per block that has a failure.
+// Every thread of the block calls it (idx < 0: the row holds, or there is no row).
+__device__ __forceinline__ void reduce_failures(int idx, uint32_t i, int K,
+                                                unsigned long long* __restrict__ res) {
+  const bool fail = idx >= 0;
+  const unsigned long long key =
+      wave_min(fail ? (unsigned long long)i * (unsigned)K + (unsigned)idx : ~0ull);
+  const unsigned long long votes = __ballot(fail);
+  __shared__ unsigned long long s_key[4];
+  __shared__ uint32_t s_cnt[4];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    s_key[wave] = key;
+    s_cnt[wave] = (uint32_t)__popcll(votes);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long k = s_key[0];
+    uint32_t cnt = s_cnt[0];
+    for (int w = 1; w < 4; w++) {
+      k = s_key[w] < k ? s_key[w] : k;
+      cnt += s_cnt[w];
+    }
+    if (cnt) {
+      atomicMin(&res[0], k);
+      atomicAdd(&res[1], (unsigned long long)cnt);
+    }
+  }
+}
+#endif
 
 }  // namespace bfz

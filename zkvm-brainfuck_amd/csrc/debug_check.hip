@@ -43,46 +43,6 @@ constexpr bool uses_kind(int kind) {
   return false;
 }
 
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-
-// The block's failing rows into res: wave minimum of row * K + index and ballot popcount, block
-// minimum over the four waves, then one atomicMin / atomicAdd per block that has a failure.
-// Every thread of the block calls it (idx < 0: the row holds, or there is no row).
-__device__ __forceinline__ void reduce_failures(int idx, uint32_t i, int K,
-                                                unsigned long long* __restrict__ res) {
-  const bool fail = idx >= 0;
-  const unsigned long long key =
-      wave_min(fail ? (unsigned long long)i * (unsigned)K + (unsigned)idx : ~0ull);
-  const unsigned long long votes = __ballot(fail);
-  __shared__ unsigned long long s_key[4];
-  __shared__ uint32_t s_cnt[4];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    s_key[wave] = key;
-    s_cnt[wave] = (uint32_t)__popcll(votes);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long k = s_key[0];
-    uint32_t cnt = s_cnt[0];
-    for (int w = 1; w < 4; w++) {
-      k = s_key[w] < k ? s_key[w] : k;
-      cnt += s_cnt[w];
-    }
-    if (cnt) {
-      atomicMin(&res[0], k);
-      atomicAdd(&res[1], (unsigned long long)cnt);
-    }
-  }
-}
-
 // ------------------------------------------------------------------------ row check
 template <int CHIP>
 __global__ __launch_bounds__(256) void k_check(const uint32_t* __restrict__ mainc,
@@ -240,30 +200,74 @@ static void fill_air_header(int chip, size_t h, ChipCheck& out) {
 
 #define BFZ_AIR_CHIPS(X) X(CHIP_CPU) X(CHIP_ADDSUB) X(CHIP_JUMP) X(CHIP_MEMINSTRS) X(CHIP_IO)
 
-void check_air_host(int chip, const uint32_t* main, size_t h, ChipCheck& out, int32_t* per_row) {
-  fill_air_header(chip, h, out);
+// The rows of a constraint program on the host (air_run over BaseOps), as rows_air_host.
+static void rows_prog_host(const AirProgram& p, const uint32_t* main, size_t h, ChipCheck& out,
+                           int32_t* per_row) {
+  const size_t w = (size_t)p.width;
+  out.failing_rows = 0;
+  out.first_row = -1;
+  out.first_constraint = -1;
+  for (size_t i = 0; i < h; i++) {
+    const size_t nx = (i + 1) & (h - 1);
+    const int idx = air_first_fail(p, main + i * w, main + nx * w, i == 0, i == h - 1);
+    if (per_row) per_row[i] = idx;
+    if (idx >= 0 && out.failing_rows++ == 0) {
+      out.first_row = (int64_t)i;
+      out.first_constraint = idx;
+    }
+  }
+}
+
+static void fill_air_header(const UniAir& air, size_t h, ChipCheck& out) {
+  if (air.prog) {
+    if (h < 1 || (h & (h - 1)) || h > ((size_t)1 << 23))
+      throw std::runtime_error("check: height not a power of two in [1, 2^23]");
+    out = ChipCheck();
+    out.height = h;
+    out.num_constraints = air.num_constraints;
+  } else {
+    fill_air_header(air.chip, h, out);
+  }
+}
+
+void check_air_host(const UniAir& air, const uint32_t* main, size_t h, ChipCheck& out,
+                    int32_t* per_row) {
+  fill_air_header(air, h, out);
+  if (air.prog) return rows_prog_host(*air.prog, main, h, out, per_row);
 #define BFZ_AIR_CASE(C) \
   case C: rows_air_host<C>(main, h, out, per_row); break;
-  switch (chip) { BFZ_AIR_CHIPS(BFZ_AIR_CASE) }
+  switch (air.chip) { BFZ_AIR_CHIPS(BFZ_AIR_CASE) }
 #undef BFZ_AIR_CASE
 }
 
-void check_air_resident(int chip, const uint32_t* mainc, size_t h, ChipCheck& out, int32_t* per_row,
-                        hipStream_t st) {
-  fill_air_header(chip, h, out);
+void check_air_host(int chip, const uint32_t* main, size_t h, ChipCheck& out, int32_t* per_row) {
+  check_air_host(uni_air_of_chip(chip), main, h, out, per_row);
+}
+
+void check_air_resident(const UniAir& air, const uint32_t* mainc, size_t h, ChipCheck& out,
+                        int32_t* per_row, hipStream_t st) {
+  fill_air_header(air, h, out);
   DBuf<unsigned long long> resd(2);
   DBuf<int32_t> rowd;
+  DBuf<uint32_t> code_d;
   if (per_row) rowd.reset(h);
   unsigned long long res[2] = {~0ull, 0};
   HIP_CHECK(hipMemcpyAsync(resd.p, res, sizeof(res), hipMemcpyHostToDevice, st));
+  if (air.prog) {  // the instruction list, uploaded once per call
+    const std::vector<uint32_t>& code = air.prog->code;
+    code_d.reset(code.size());
+    HIP_CHECK(hipMemcpyAsync(code_d.p, code.data(), code.size() * 4, hipMemcpyHostToDevice, st));
+    launch_check_prog(code_d.p, (int)code.size(), mainc, h, out.num_constraints, resd.p, rowd.p, st);
+  } else {
 #define BFZ_AIR_CASE(C)                                                                        \
   case C:                                                                                      \
     hipLaunchKernelGGL(k_check_air<C>, dim3(ceil_div(h, 256)), dim3(256), 0, st, mainc,        \
                        (uint32_t)h, log2i(h), out.num_constraints, resd.p, rowd.p);            \
     break;
-  switch (chip) { BFZ_AIR_CHIPS(BFZ_AIR_CASE) }
+    switch (air.chip) { BFZ_AIR_CHIPS(BFZ_AIR_CASE) }
 #undef BFZ_AIR_CASE
-  KCHECK();
+    KCHECK();
+  }
   std::vector<int32_t> rows(per_row ? h : 0);
   HIP_CHECK(hipMemcpyAsync(res, resd.p, sizeof(res), hipMemcpyDeviceToHost, st));
   if (per_row) HIP_CHECK(hipMemcpyAsync(rows.data(), rowd.p, h * 4, hipMemcpyDeviceToHost, st));
@@ -273,6 +277,11 @@ void check_air_resident(int chip, const uint32_t* mainc, size_t h, ChipCheck& ou
     const int logh = log2i(h);
     for (size_t r = 0; r < h; r++) per_row[r] = rows[bitrev32((uint32_t)r, logh)];  // storage -> natural
   }
+}
+
+void check_air_resident(int chip, const uint32_t* mainc, size_t h, ChipCheck& out, int32_t* per_row,
+                        hipStream_t st) {
+  check_air_resident(uni_air_of_chip(chip), mainc, h, out, per_row, st);
 }
 #undef BFZ_AIR_CHIPS
 

@@ -6,6 +6,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "../../include/bfz.h"
 #include "machine.h"
 
 namespace bfz {
@@ -192,7 +193,8 @@ UniProof decode_bfu1(const uint8_t* p, size_t n) {
   UniProof u;
   if (r.u32() != BFU1_MAGIC) throw std::runtime_error("bad magic");
   u.chip = r.u32();
-  if (u.chip >= (uint32_t)NUM_CHIPS) throw std::runtime_error("bad chip id");
+  // BFZ_AIR_CHIP labels a proof made from a constraint program (bfz_air_prove)
+  if (u.chip >= (uint32_t)NUM_CHIPS && u.chip != BFZ_AIR_CHIP) throw std::runtime_error("bad chip id");
   u.log_degree = r.u32();
   u.pcs.main_root = r.digest();  // the trace commitment
   u.pcs.quot_root = r.digest();  // the quotient commitment

@@ -56,6 +56,11 @@ void quotient_into(int chip, const QuotRows& in, int logN, const QuotParams& qp,
 // alpha^(K-1-k)), zh_*, wn_inv and shift are read; qp_dev is the same in device memory.
 void quotient_air(int chip, int lqd, const uint32_t* mainc, int logN, const QuotParams& qp,
                   const QuotParams* qp_dev, const QuotOut& out, hipStream_t st);
+// The same for a compiled constraint program (air_program.h): code_dev = its instruction list in
+// device memory, ncode words.
+void quotient_prog(const uint32_t* code_dev, int ncode, int lqd, const uint32_t* mainc, int logN,
+                   const QuotParams& qp, const QuotParams* qp_dev, const QuotOut& out,
+                   hipStream_t st);
 // Constraints Air::eval_air<chip> emits, their maximal degree and log2_ceil(degree - 1)
 // (chip.rs:82-87), computed from air.h.  false: the chip has no AIR constraints of its own.
 bool uni_air_shape(int chip, int* num_constraints, int* degree, int* log_quotient_degree);
@@ -73,5 +78,65 @@ struct QuotAlphaTargets {
 void challenge_quot(DevChallenger* ch, const uint32_t* root, const kb::EF* cums, int nc,
                     const PermChallenges* pc, QuotParams* qps, const QuotAlphaTargets& tg,
                     hipStream_t st);
+
+#if defined(__HIPCC__)
+// ---- device helpers shared by the quotient kernels (quotient.hip, air_program.hip)
+// Lazy fold of the constraints: raw 64-bit products of Montgomery values accumulate with
+// v_mad_u64_u32 (a base constraint times its EF alpha power is one multiply-add per
+// component instead of a Montgomery product + modular add).  Budget: a raw product is < p^2
+// (1 unit), a reduced EF term added at scale 2^32 is < 2 p^2 (2 units); the accumulator is
+// folded (hi * (2^32 mod p) + lo < 2^57) before 4 units would be exceeded (4 p^2 + 2^57 <
+// 2^64), and reduced once at the end -- the same field element as the eager sum.
+struct PowAcc {
+  static constexpr uint32_t C32 = (1u << 25) - 2;  // 2^32 mod p
+  uint64_t a64[4];
+  int units;
+  // alpha powers, read through the constant address space: the pointer now comes from device
+  // memory (QuotParams), and through a generic pointer the reads became vector flat loads (+19
+  // VGPRs, k_quotient<0> 930 -> 1031 us); as constant-space loads they stay scalar.
+  const __attribute__((address_space(4))) uint32_t* ap;
+  int k;
+  __device__ __forceinline__ kb::EF pow_k() {
+    kb::EF a;
+#pragma unroll
+    for (int e = 0; e < 4; e++) a.c[e] = ap[4 * k + e];
+    k++;
+    return a;
+  }
+  __device__ __forceinline__ void fold() {
+#pragma unroll
+    for (int e = 0; e < 4; e++) a64[e] = (uint64_t)(uint32_t)(a64[e] >> 32) * C32 + (uint32_t)a64[e];
+    units = 0;
+  }
+  __device__ __forceinline__ void emit(uint32_t c) {
+    if (units + 1 > 4) fold();
+    const kb::EF a = pow_k();
+#pragma unroll
+    for (int e = 0; e < 4; e++) a64[e] += (uint64_t)a.c[e] * c;
+    units += 1;
+  }
+  __device__ __forceinline__ void emit_ext(const kb::EF& c) {
+    if (units + 2 > 4) fold();
+    const kb::EF r = kb::ef_mul(pow_k(), c);
+#pragma unroll
+    for (int e = 0; e < 4; e++) a64[e] += (uint64_t)r.c[e] << 32;
+    units += 2;
+  }
+  __device__ __forceinline__ kb::EF value() {
+    fold();
+    kb::EF r;
+#pragma unroll
+    for (int e = 0; e < 4; e++) r.c[e] = kb::mred_lt_p(a64[e]);  // folded: < 2^57
+    return r;
+  }
+};
+
+// x_i = 3 w_N^i, the natural point i of the quotient domain 3 H_N (twf[N/2 + j] = w_N^j).
+__device__ __forceinline__ uint32_t quot_point(uint32_t i, uint32_t half, uint32_t shift,
+                                               const uint32_t* __restrict__ twf) {
+  const uint32_t w = i < half ? twf[half + i] : kb::mneg(twf[i]);  // twf[half + (i - half)]
+  return kb::mmul(shift, w);
+}
+#endif
 
 }  // namespace bfz

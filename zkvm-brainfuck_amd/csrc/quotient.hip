@@ -18,6 +18,7 @@
 #include <map>
 
 #include "air.h"
+#include "air_program.h"
 
 namespace bfz {
 
@@ -26,63 +27,6 @@ using namespace kb;
 constexpr int QMAIN_W[NUM_CHIPS] = {31, 1, 7, 45, 12, 2, 41, 5};
 constexpr int QPREP_W[NUM_CHIPS] = {0, 6, 0, 0, 0, 2, 0, 0};
 constexpr int QPERM_W[NUM_CHIPS] = {9, 2, 4, 2, 3, 2, 2, 2};
-
-// Lazy fold of the constraints: raw 64-bit products of Montgomery values accumulate with
-// v_mad_u64_u32 (a base constraint times its EF alpha power is one multiply-add per
-// component instead of a Montgomery product + modular add).  Budget: a raw product is < p^2
-// (1 unit), a reduced EF term added at scale 2^32 is < 2 p^2 (2 units); the accumulator is
-// folded (hi * (2^32 mod p) + lo < 2^57) before 4 units would be exceeded (4 p^2 + 2^57 <
-// 2^64), and reduced once at the end -- the same field element as the eager sum.
-struct PowAcc {
-  static constexpr uint32_t C32 = (1u << 25) - 2;  // 2^32 mod p
-  uint64_t a64[4];
-  int units;
-  // alpha powers, read through the constant address space: the pointer now comes from device
-  // memory (QuotParams), and through a generic pointer the reads became vector flat loads (+19
-  // VGPRs, k_quotient<0> 930 -> 1031 us); as constant-space loads they stay scalar.
-  const __attribute__((address_space(4))) uint32_t* ap;
-  int k;
-  __device__ __forceinline__ EF pow_k() {
-    EF a;
-#pragma unroll
-    for (int e = 0; e < 4; e++) a.c[e] = ap[4 * k + e];
-    k++;
-    return a;
-  }
-  __device__ __forceinline__ void fold() {
-#pragma unroll
-    for (int e = 0; e < 4; e++) a64[e] = (uint64_t)(uint32_t)(a64[e] >> 32) * C32 + (uint32_t)a64[e];
-    units = 0;
-  }
-  __device__ __forceinline__ void emit(uint32_t c) {
-    if (units + 1 > 4) fold();
-    const EF a = pow_k();
-#pragma unroll
-    for (int e = 0; e < 4; e++) a64[e] += (uint64_t)a.c[e] * c;
-    units += 1;
-  }
-  __device__ __forceinline__ void emit_ext(const EF& c) {
-    if (units + 2 > 4) fold();
-    const EF r = ef_mul(pow_k(), c);
-#pragma unroll
-    for (int e = 0; e < 4; e++) a64[e] += (uint64_t)r.c[e] << 32;
-    units += 2;
-  }
-  __device__ __forceinline__ EF value() {
-    fold();
-    EF r;
-#pragma unroll
-    for (int e = 0; e < 4; e++) r.c[e] = mred_lt_p(a64[e]);  // folded: < 2^57
-    return r;
-  }
-};
-
-// x_i = 3 w_N^i, the natural point i of the quotient domain 3 H_N (twf[N/2 + j] = w_N^j).
-__device__ __forceinline__ uint32_t quot_point(uint32_t i, uint32_t half, uint32_t shift,
-                                               const uint32_t* __restrict__ twf) {
-  const uint32_t w = i < half ? twf[half + i] : mneg(twf[i]);  // twf[half + (i - half)]
-  return mmul(shift, w);
-}
 
 // 1 / ((x - 1)(x - w_n^-1)) at every point of 3 H_N, stored by LDE position t (point
 // bitrev(t)): the selector denominators depend on the domain alone, so one table per log N
@@ -312,6 +256,19 @@ void quotient_air(int chip, int lqd, const uint32_t* mainc, int logN, const Quot
     case CHIP_IO: launch_qa<CHIP_IO>(lqd, mainc, logN, qp_dev, sel, qout, st); break;
     default: throw std::runtime_error("quotient_air: the chip has no AIR constraints");
   }
+}
+
+// quotient_air for an AIR that arrives as a constraint program (air_program.h): the same
+// tables, k_quotient_prog<lqd> instead of the chip's compiled template.
+void quotient_prog(const uint32_t* code_dev, int ncode, int lqd, const uint32_t* mainc, int logN,
+                   const QuotParams& qp, const QuotParams* qp_dev, const QuotOut& qout,
+                   hipStream_t st) {
+  if (lqd < 0 || lqd > 1) throw std::runtime_error("quotient_prog: log quotient degree not 0 or 1");
+  if (logN < 1 || logN > 24) throw std::runtime_error("quotient_prog: bad LDE height");
+  twiddles().ensure(logN);
+  const uint32_t* sel = sel_inv_table(logN, qp, st);
+  launch_quotient_prog(lqd, code_dev, ncode, mainc, logN, qp_dev, (const uint32_t*)twiddles().fwd(),
+                       sel, qout, st);
 }
 
 // The quotient challenge on the device (challenger.h): the sponge observes the permutation

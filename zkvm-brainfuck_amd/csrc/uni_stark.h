@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "air_program.h"
 #include "prover.h"
 #include "verifier.h"
 
@@ -27,9 +28,24 @@ struct UniOptions {
 // bad index and for Program, Memory and Byte.  Any output pointer may be null.
 void uni_air_shape_or_throw(int chip, int* num_constraints, int* degree, int* log_quotient_degree);
 
+// What the prover, the row check and the verifier take from an AIR: its shape and name, and which
+// code evaluates it -- a built-in chip (chip >= 0: the compiled templates of air.h) or a compiled
+// constraint program (prog, chip = -1; the program outlives the call).
+struct UniAir {
+  int chip = -1;
+  const AirProgram* prog = nullptr;
+  int num_constraints = 0, degree = 0, log_quotient_degree = 0, width = 0;
+  const char* name = "custom";
+};
+UniAir uni_air_of_chip(int chip);  // throws as uni_air_shape_or_throw
+UniAir uni_air_of_program(const AirProgram& p);
+
 // trace: row-major Montgomery height x width on the host.  ch is advanced to the state after
 // the whole opening (as open_main's `after`).  Returns the BFU1 bytes.  The API lock is held.
 std::vector<uint8_t> uni_prove(int chip, const uint32_t* trace, size_t height, size_t width,
+                               Challenger& ch, const UniOptions& opt, StageTimes* times);
+// The same for any AIR; a program's proof carries the chip word BFZ_AIR_CHIP.
+std::vector<uint8_t> uni_prove(const UniAir& air, const uint32_t* trace, size_t height, size_t width,
                                Challenger& ch, const UniOptions& opt, StageTimes* times);
 
 // The same from device evaluations: evals = n x main_w of the chip, column-major and bit-reversed
@@ -41,14 +57,19 @@ std::vector<uint8_t> uni_prove_evals(int chip, const uint32_t* evals, size_t n, 
 // The input checks every uni-STARK call shares, with uni_prove's messages: the chip
 // (uni_air_shape_or_throw), a constraint degree above 3, the width, the height.
 void uni_dims_or_throw(int chip, size_t height, size_t width);
-[[noreturn]] void uni_noncanonical_throw(int chip);  // a trace word >= p
-// uni_prove's upload: the row-major host trace to the device, refused when a word is >= p
-// (syncs st), transposed into the library layout.
-DBuf<uint32_t> uni_upload_trace(int chip, const uint32_t* trace, size_t n, hipStream_t st);
+void uni_dims_or_throw(const UniAir& air, size_t height, size_t width);
+[[noreturn]] void uni_noncanonical_throw(const char* name);  // a trace word >= p
+// uni_prove's upload: the row-major host trace (n x width) to the device, refused when a word is
+// >= p (syncs st; name is the AIR's, for the message), transposed into the library layout.
+DBuf<uint32_t> uni_upload_trace(size_t width, const char* name, const uint32_t* trace, size_t n,
+                                hipStream_t st);
 
 // Host verifier (verifier.cpp).  ch is advanced as far as the check got; on acceptance it is the
 // prover's final state.
 VerifyOutcome uni_verify(int chip, Challenger& ch, const uint8_t* proof, size_t len,
+                         const UniOptions& opt);
+// The same against a constraint program: the proof's chip word is a label and is not interpreted.
+VerifyOutcome uni_verify(const UniAir& air, Challenger& ch, const uint8_t* proof, size_t len,
                          const UniOptions& opt);
 
 // n BFU1 proofs, proof i of chip chips[i] against challenger chs[i] (advanced), with

@@ -89,32 +89,54 @@ struct Rewind {  // the pinned upload arena is rewound when the call is done (as
   }
 };
 
-std::vector<uint8_t> prove_core(int chip, const uint32_t* evals, size_t n, Challenger& ch_io,
-                                const UniOptions& opt, StageTimes* tms, StageClock& clock);
+std::vector<uint8_t> prove_core(const UniAir& air, const uint32_t* evals, size_t n,
+                                Challenger& ch_io, const UniOptions& opt, StageTimes* tms,
+                                StageClock& clock);
 }  // namespace
 
-void uni_dims_or_throw(int chip, size_t height, size_t width) {
-  int k = 0, degree = 0, l = 0;
-  uni_air_shape_or_throw(chip, &k, &degree, &l);
-  if (l > 1) throw std::runtime_error("uni_stark: constraint degree above 3 is not supported");
-  if ((size_t)CHIP_INFO[chip].main_w != width)
-    throw std::runtime_error(std::string("uni_stark: width mismatch for ") + CHIP_INFO[chip].name);
+UniAir uni_air_of_chip(int chip) {
+  UniAir a;
+  uni_air_shape_or_throw(chip, &a.num_constraints, &a.degree, &a.log_quotient_degree);
+  a.chip = chip;
+  a.width = CHIP_INFO[chip].main_w;
+  a.name = CHIP_INFO[chip].name;
+  return a;
+}
+
+UniAir uni_air_of_program(const AirProgram& p) {
+  UniAir a;
+  a.prog = &p;
+  a.num_constraints = p.num_constraints;
+  a.degree = p.degree;
+  a.log_quotient_degree = p.log_quotient_degree;
+  a.width = p.width;
+  return a;
+}
+
+void uni_dims_or_throw(const UniAir& air, size_t height, size_t width) {
+  if (air.log_quotient_degree > 1)
+    throw std::runtime_error("uni_stark: constraint degree above 3 is not supported");
+  if ((size_t)air.width != width)
+    throw std::runtime_error(std::string("uni_stark: width mismatch for ") + air.name);
   if (height < 1 || (height & (height - 1)) || height > ((size_t)1 << 23))
     throw std::runtime_error(std::string("uni_stark: height not a power of two in [1, 2^23] for ") +
-                             CHIP_INFO[chip].name);
+                             air.name);
 }
 
-void uni_noncanonical_throw(int chip) {
-  throw std::runtime_error(std::string("uni_stark: non-canonical field word (>= p) in ") +
-                           CHIP_INFO[chip].name);
+void uni_dims_or_throw(int chip, size_t height, size_t width) {
+  uni_dims_or_throw(uni_air_of_chip(chip), height, width);
 }
 
-DBuf<uint32_t> uni_upload_trace(int chip, const uint32_t* trace, size_t n, hipStream_t st) {
-  const int w = CHIP_INFO[chip].main_w;
-  DBuf<uint32_t> evals(n * (size_t)w), rm(n * (size_t)w);
-  upload_bulk(rm.p, trace, n * (size_t)w * 4, st);
+void uni_noncanonical_throw(const char* name) {
+  throw std::runtime_error(std::string("uni_stark: non-canonical field word (>= p) in ") + name);
+}
+
+DBuf<uint32_t> uni_upload_trace(size_t w, const char* name, const uint32_t* trace, size_t n,
+                                hipStream_t st) {
+  DBuf<uint32_t> evals(n * w), rm(n * w);
+  upload_bulk(rm.p, trace, n * w * 4, st);
   // KoalaBear words are Montgomery residues < p; a larger word breaks mmul's b < p bound
-  if (count_noncanonical(rm.p, n * (size_t)w, st)) uni_noncanonical_throw(chip);
+  if (count_noncanonical(rm.p, n * w, st)) uni_noncanonical_throw(name);
   transpose_bitrev(rm.p, n, w, evals.p, st);
   return evals;
 }
@@ -124,14 +146,21 @@ std::vector<uint8_t> uni_prove(int chip, const uint32_t* trace, size_t height, s
                                Challenger& ch, const UniOptions& opt, StageTimes* times) {
   if (api_lock_depth() == 0) throw std::logic_error("uni_prove called outside the bfz API lock");
   if (!trace) throw std::runtime_error("uni_stark: null trace");
-  uni_dims_or_throw(chip, height, width);
+  return uni_prove(uni_air_of_chip(chip), trace, height, width, ch, opt, times);
+}
+
+std::vector<uint8_t> uni_prove(const UniAir& air, const uint32_t* trace, size_t height, size_t width,
+                               Challenger& ch, const UniOptions& opt, StageTimes* times) {
+  if (api_lock_depth() == 0) throw std::logic_error("uni_prove called outside the bfz API lock");
+  if (!trace) throw std::runtime_error("uni_stark: null trace");
+  uni_dims_or_throw(air, height, width);
   if (opt.num_queries < 1 || opt.num_queries > 4096) throw std::runtime_error("uni_stark: bad query count");
   hipStream_t st = stream();
   Rewind rewind{st};
   StageTimes local;
   StageClock clock(times != nullptr, st);
-  const DBuf<uint32_t> evals = uni_upload_trace(chip, trace, height, st);
-  return prove_core(chip, evals.p, height, ch, opt, times ? times : &local, clock);
+  const DBuf<uint32_t> evals = uni_upload_trace(width, air.name, trace, height, st);
+  return prove_core(air, evals.p, height, ch, opt, times ? times : &local, clock);
 }
 
 // The device front: the evaluations are where they are, nothing is uploaded, transposed or copied.
@@ -139,24 +168,23 @@ std::vector<uint8_t> uni_prove_evals(int chip, const uint32_t* evals, size_t n, 
                                      const UniOptions& opt, StageTimes* times) {
   if (api_lock_depth() == 0) throw std::logic_error("uni_prove called outside the bfz API lock");
   if (!evals) throw std::runtime_error("uni_stark: null trace");
-  uni_air_shape_or_throw(chip, nullptr, nullptr, nullptr);  // before CHIP_INFO is indexed
-  uni_dims_or_throw(chip, n, (size_t)CHIP_INFO[chip].main_w);
+  const UniAir air = uni_air_of_chip(chip);
+  uni_dims_or_throw(air, n, (size_t)air.width);
   if (opt.num_queries < 1 || opt.num_queries > 4096) throw std::runtime_error("uni_stark: bad query count");
   hipStream_t st = stream();
   Rewind rewind{st};
   StageTimes local;
   StageClock clock(times != nullptr, st);
-  return prove_core(chip, evals, n, ch, opt, times ? times : &local, clock);
+  return prove_core(air, evals, n, ch, opt, times ? times : &local, clock);
 }
 
 namespace {
 // The prover from device evaluations (evals, n) in the library layout (column-major,
 // bit-reversed): everything after the fronts.  The inputs have been checked.
-std::vector<uint8_t> prove_core(int chip, const uint32_t* evals, size_t n, Challenger& ch_io,
-                                const UniOptions& opt, StageTimes* tms, StageClock& clock) {
-  int K = 0, degree = 0, lqd = 0;
-  uni_air_shape_or_throw(chip, &K, &degree, &lqd);
-  const int w = CHIP_INFO[chip].main_w;
+std::vector<uint8_t> prove_core(const UniAir& air, const uint32_t* evals, size_t n,
+                                Challenger& ch_io, const UniOptions& opt, StageTimes* tms,
+                                StageClock& clock) {
+  const int K = air.num_constraints, lqd = air.log_quotient_degree, w = air.width;
   const int logn = log2i(n), Lmax = logn + LOG_BLOWUP;
   const size_t N = 2 * n;
   const int nchunks = 1 << lqd;
@@ -221,7 +249,14 @@ std::vector<uint8_t> prove_core(int chip, const uint32_t* evals, size_t n, Chall
     qo.chunk[0] = quotr.mats[0].lde.buf.p;
     qo.chunk[1] = nchunks > 1 ? quotr.mats[1].lde.buf.p + n : nullptr;
     qo.stride = N;
-    quotient_air(chip, lqd, tracer.mats[0].lde.buf.p, Lmax, qp, qp_d.p, qo, st);
+    if (air.prog) {  // the instruction list, uploaded once per call on the proof's stream
+      const std::vector<uint32_t>& code = air.prog->code;
+      DBuf<uint32_t> code_d(code.size());  // (stream-ordered: freed after the launch is fine)
+      upload_async(code_d.p, code.data(), code.size() * 4, st);
+      quotient_prog(code_d.p, (int)code.size(), lqd, tracer.mats[0].lde.buf.p, Lmax, qp, qp_d.p, qo, st);
+    } else {
+      quotient_air(air.chip, lqd, tracer.mats[0].lde.buf.p, Lmax, qp, qp_d.p, qo, st);
+    }
   }
   for (int j = 0; j < nchunks; j++) {  // the other half of each chunk's LDE on 3 H_2n
     CMat& qm = quotr.mats[j];
@@ -532,7 +567,7 @@ std::vector<uint8_t> prove_core(int chip, const uint32_t* evals, size_t n, Chall
 
   // ---- serialize (BFU1 normal form, proof.cpp)
   UniProof u;
-  u.chip = (uint32_t)chip;
+  u.chip = air.prog ? BFZ_AIR_CHIP : (uint32_t)air.chip;
   u.log_degree = (uint32_t)logn;
   std::memcpy(u.pcs.main_root.data(), tracer.tree.root, 32);
   std::memcpy(u.pcs.quot_root.data(), quotr.tree.root, 32);

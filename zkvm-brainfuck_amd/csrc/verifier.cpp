@@ -818,6 +818,21 @@ EF fold_air_any(int chip, const std::vector<EF>& ml, const std::vector<EF>& mn, 
   }
   throw std::runtime_error("bad chip");
 }
+// The same fold for a constraint program: its K values at zeta by Horner (acc = acc * alpha + c).
+EF fold_program(const AirProgram& p, const std::vector<EF>& ml, const std::vector<EF>& mn,
+                const EF& first, const EF& last, const EF& trans, const EF& alpha) {
+  std::vector<EF> c((size_t)p.num_constraints);
+  air_eval_ef(p, ml.data(), mn.data(), first, last, trans, c.data());
+  EF acc = ef_zero();
+  for (const EF& v : c) acc = ef_add(ef_mul(acc, alpha), v);
+  return acc;
+}
+UniAir verifier_air_of_chip(int chip) {  // a refusal here is the proof's verdict, not an error
+  int K = 0, degree = 0, lqd = 0;
+  if (!uni_air_shape(chip, &K, &degree, &lqd) || lqd > 1)
+    throw std::runtime_error("chip has no uni-STARK AIR");
+  return uni_air_of_chip(chip);
+}
 }  // namespace
 
 // p3_uni_stark::verify [p3-recalled] as utils::uni_stark_verify calls it (utils/prove.rs:129-159),
@@ -829,24 +844,25 @@ namespace {
 struct UniState {
   UniProof u;
   ShardState S;
-  int chip = -1, log_n = 0, nchunks = 0;
+  UniAir air;
+  int log_n = 0, nchunks = 0;
   EF alpha;
   std::vector<uint32_t> sh;  // chunk j's domain shift
 };
 
-void uni_before_queries(int chip, Challenger& ch, const uint8_t* proof, size_t len,
+void uni_before_queries(const UniAir& air, Challenger& ch, const uint8_t* proof, size_t len,
                         const UniOptions& opt, UniState& U) {
-  int K = 0, degree = 0, lqd = 0;
-  if (!uni_air_shape(chip, &K, &degree, &lqd) || lqd > 1)
-    throw std::runtime_error("chip has no uni-STARK AIR");
+  const int lqd = air.log_quotient_degree;
+  if (lqd > 1) throw std::runtime_error("chip has no uni-STARK AIR");
   U.u = decode_bfu1(proof, len);
   const UniProof& u = U.u;
-  if ((int)u.chip != chip) throw std::runtime_error("proof is for another chip");
+  // a program's proof: the chip word is a label outside the transcript and is not interpreted
+  if (!air.prog && u.chip != (uint32_t)air.chip) throw std::runtime_error("proof is for another chip");
   // unsigned: a huge word must not become a negative shift count below
   if (u.log_degree > 23) throw std::runtime_error("log degree out of range");
   const int log_n = U.log_n = (int)u.log_degree, nchunks = U.nchunks = 1 << lqd;
-  U.chip = chip;
-  const size_t w = (size_t)CHIP_INFO[chip].main_w;
+  U.air = air;
+  const size_t w = (size_t)air.width;
   if (u.trace_local.size() != w || u.trace_next.size() != w || u.chunks.size() != (size_t)nchunks)
     throw std::runtime_error("opened-value shape mismatch");
   for (const std::vector<EF>& c : u.chunks)
@@ -880,7 +896,7 @@ void uni_before_queries(int chip, Challenger& ch, const uint8_t* proof, size_t l
 // The quotient at zeta from its chunks, the selectors, the folded constraints.
 void uni_after_queries(const UniState& U) {
   const UniProof& u = U.u;
-  const int log_n = U.log_n, nchunks = U.nchunks, chip = U.chip;
+  const int log_n = U.log_n, nchunks = U.nchunks;
   const std::vector<uint32_t>& sh = U.sh;
   const EF zeta = U.S.zeta;
   EF quot = ef_zero();
@@ -898,18 +914,23 @@ void uni_after_queries(const UniState& U) {
   const EF first = ef_mul(zh, ef_inv(ef_sub(zeta, ef_one())));
   const EF last = ef_mul(zh, ef_inv(ef_sub(zeta, ef_base(gn_inv))));
   const EF trans = ef_sub(zeta, ef_base(gn_inv));
-  const EF folded = fold_air_any(chip, u.trace_local, u.trace_next, first, last, trans, U.alpha);
+  const EF folded =
+      U.air.prog ? fold_program(*U.air.prog, u.trace_local, u.trace_next, first, last, trans, U.alpha)
+                 : fold_air_any(U.air.chip, u.trace_local, u.trace_next, first, last, trans, U.alpha);
   if (!ef_eq(ef_mul(folded, ef_inv(zh)), quot))
-    throw std::runtime_error(std::string("OOD evaluation mismatch on chip ") + CHIP_INFO[chip].name);
+    throw std::runtime_error(std::string("OOD evaluation mismatch on chip ") + U.air.name);
 }
 }  // namespace
 
-VerifyOutcome uni_verify(int chip, Challenger& ch, const uint8_t* proof, size_t len,
-                         const UniOptions& opt) {
+namespace {
+// air_of: the AIR, made inside the try (a chip without one is a verdict)
+template <class AirOf>
+VerifyOutcome uni_verify_with(AirOf&& air_of, Challenger& ch, const uint8_t* proof, size_t len,
+                              const UniOptions& opt) {
   VerifyOutcome o;
   try {
     UniState U;
-    uni_before_queries(chip, ch, proof, len, opt, U);
+    uni_before_queries(air_of(), ch, proof, len, opt, U);
     for (uint32_t q = 0; q < U.S.nq; q++) {
       o.query = (int)q;
       check_query(U.S, q);
@@ -922,6 +943,17 @@ VerifyOutcome uni_verify(int chip, Challenger& ch, const uint8_t* proof, size_t 
   }
   return o;
 }
+}  // namespace
+
+VerifyOutcome uni_verify(int chip, Challenger& ch, const uint8_t* proof, size_t len,
+                         const UniOptions& opt) {
+  return uni_verify_with([&] { return verifier_air_of_chip(chip); }, ch, proof, len, opt);
+}
+
+VerifyOutcome uni_verify(const UniAir& air, Challenger& ch, const uint8_t* proof, size_t len,
+                         const UniOptions& opt) {
+  return uni_verify_with([&] { return air; }, ch, proof, len, opt);
+}
 
 std::vector<VerifyOutcome> uni_verify_batch(const int* chips, Challenger* chs,
                                             const uint8_t* const* proofs, const size_t* lens,
@@ -933,7 +965,9 @@ std::vector<VerifyOutcome> uni_verify_batch(const int* chips, Challenger* chs,
   }
   return batch_on_device<UniState>(
       lens, n, run_queries,
-      [&](size_t i, UniState& U) { uni_before_queries(chips[i], chs[i], proofs[i], lens[i], opt, U); },
+      [&](size_t i, UniState& U) {
+        uni_before_queries(verifier_air_of_chip(chips[i]), chs[i], proofs[i], lens[i], opt, U);
+      },
       [](size_t, const UniState& U) { uni_after_queries(U); });
 }
 
