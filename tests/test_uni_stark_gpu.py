@@ -132,6 +132,36 @@ def test_one_chunk_shape_at_the_smallest_heights(height):
     assert model_checks(IO, trace, proof, ch_p) == "cd"
 
 
+@pytest.mark.parametrize("name,chip", [("io-zero-65536", IO), ("cpu-65536", CPU)])
+def test_fused_fold_rounds_reproduce_the_recorded_proofs(name, chip):
+    """2^16 rows is the smallest height whose first commit-phase round leaves a fold of
+    2^15 >= FRI_FUSE_MIN outputs pending: the fused fold + leaf-hash round runs, then the unfused
+    rounds and the single-launch tail.  One chunk (all-zero IO rows) and two chunks (Cpu).  The
+    digests of tests/golden/uni_stark_fused.json were recorded before the uni-STARK prover took
+    over the machine prover's PCS opening, from the build of the commit named there."""
+    import hashlib
+    import json
+    if chip == IO:
+        trace = np.zeros((1 << 16, 5), dtype=np.uint32)
+    else:
+        trace = trace_of(CPU, guests.FIBO, [17])
+    assert trace.shape[0] == 1 << 16
+    here = os.path.dirname(os.path.abspath(__file__))
+    golden = json.load(open(os.path.join(here, "golden", "uni_stark_fused.json")))
+    assert golden["num_queries"] == QUERIES
+    proof, ch_p = prove(chip, trace)
+    ok, why, ch_v = verify(chip, proof)
+    assert ok, why
+    assert bytes(ch_p) == bytes(ch_v)
+    assert prove(chip, trace)[0] == proof
+    p = M.parse(proof)
+    assert len(p["queries"]) == QUERIES and p["log_degree"] == 16
+    M.check_transcript(p, M.challenger_words(ch_p))
+    want = golden["proofs"][name]
+    assert len(proof) == want["bytes"]
+    assert hashlib.sha256(proof).hexdigest() == want["sha256"]
+
+
 def test_invalid_traces_prove_and_are_rejected():
     """One changed cell of a real AddSub row, and the MemoryInstrs trace of `<+` (the pointer steps
     below cell 0: the word range check fails): both still prove, and the verifier's out-of-domain

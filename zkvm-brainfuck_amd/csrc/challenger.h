@@ -14,6 +14,8 @@ struct DevChallenger {  // the host Challenger's fields, in device memory
   uint32_t out[8];
   int32_t nout;
 };
+struct Challenger;                                   // prover.h
+DevChallenger dev_challenger(const Challenger& ch);  // the host's state, ready to upload
 
 #ifdef __HIPCC__
 struct LaneSponge {

@@ -197,7 +197,7 @@ struct Lane {
   uint8_t* box = nullptr;  // pinned mailbox of fetch
   size_t box_cap = 0;
   hipEvent_t spin = nullptr;  // spin_sync's event
-  // open_impl's pinned buffers (prover.hip): the opened-value groups and the proof's tail
+  // pcs_open's pinned buffers (pcs_open.hip): the opened-value groups and the proof's tail
   static constexpr int NGEV = 4;
   hipEvent_t gev[NGEV] = {};
   void* gbox = nullptr;
@@ -305,7 +305,7 @@ void quiesce() noexcept;
 void roctx_push(const char* name) noexcept;
 void roctx_pop() noexcept;
 // Every C entry point runs under one process-wide API lock (capi.cpp guarded()); proof code
-// that keeps process-global state (open_impl's pinned mailboxes) checks that it is held.
+// that keeps process-global state (pcs_open's pinned boxes) checks that it is held.
 // Profiler ranges named after the reference's tracing spans (crates/stark/src/prover.rs:63,281,
 // 333,355,410,460,575): roctx push / pop, recorded by `rocprofv3 --marker-trace` beside the kernel
 // trace.  They are host-side spans (launches plus the transcript's waits), as the reference's are

@@ -161,18 +161,6 @@ Challenger challenger_after_pk(const ProvingKey& pk);
 std::vector<uint8_t> open_main(const ProvingKey& pk, MainData& md, const Challenger& ch,
                                const ProveOptions& opt, Challenger* after = nullptr);
 
-// The end of the FRI commit phase packed for one device-to-host copy (open_impl's tail buffer;
-// uni_stark.hip builds the same): [root 0 .. root MAX-1 (8 words each) | state (16) | final
-// layer (2 EF)].  nroots may be 0 (state then unused, but still read: 16 valid words).
-constexpr int MAX_FRI_ROUNDS = 32;
-struct FriTail {
-  const uint32_t* root[MAX_FRI_ROUNDS];
-  int nroots;
-  const uint32_t* state;
-  const EF* fin;
-};
-void pack_fri_tail(const FriTail& t, uint32_t* packed, hipStream_t st);
-
 int num_queries_from_env();
 bool observe_openings_from_env();  // BFZ_OBSERVE_OPENINGS = 1 (default) | 0
 

@@ -20,6 +20,7 @@
 #include "host_p2.h"
 #include "logup.h"
 #include "ntt.h"
+#include "pcs_open.h"
 #include "poseidon2.h"
 #include "quotient.h"
 #include "tracegen.h"
@@ -28,9 +29,6 @@
 namespace bfz {
 
 using namespace kb;
-
-static constexpr int LOG_BLOWUP = 1;
-static constexpr int POW_BITS = 16;
 
 // kb31_poseidon2.rs:59-62: `value.parse().unwrap()` into a usize -- anything but a whole
 // positive decimal number is an error (the reference panics), never a silent 0 or default.
@@ -86,21 +84,17 @@ bool Challenger::check_witness(int bits, uint32_t w) {
   observe(to_mont(w));
   return sample_bits(bits) == 0;
 }
+DevChallenger dev_challenger(const Challenger& ch) {
+  DevChallenger dc;
+  std::memcpy(dc.st, ch.st, sizeof(dc.st));
+  std::memcpy(dc.in, ch.in, sizeof(dc.in));
+  std::memcpy(dc.out, ch.out, sizeof(dc.out));
+  dc.nin = ch.nin;
+  dc.nout = ch.nout;
+  return dc;
+}
 
 // ------------------------------------------------------------------------ timing
-// packed = [root 0 .. root MAX-1 (8 words each) | state (16) | final layer (2 EF)]; nroots may
-// be 0 (state then unused)
-__global__ void k_pack_fri_tail(FriTail t, uint32_t* __restrict__ packed) {
-  const int i = threadIdx.x;
-  if (i < 8 * t.nroots) packed[i] = t.root[i >> 3][i & 7];
-  if (i < 16) packed[8 * MAX_FRI_ROUNDS + i] = t.state[i];
-  if (i < 8) packed[8 * MAX_FRI_ROUNDS + 16 + i] = t.fin[i >> 2].c[i & 3];
-}
-void pack_fri_tail(const FriTail& t, uint32_t* packed, hipStream_t st) {
-  hipLaunchKernelGGL(k_pack_fri_tail, dim3(1), dim3(256), 0, st, t, packed);
-  KCHECK();
-}
-
 namespace {
 // BFZ_HOST_TRACE=1: host timestamps (us since the last mark 0) at the transcript points of each
 // proof, printed on stderr at exit -- splits the GPU's idle gaps into host work and launch
@@ -165,38 +159,6 @@ void release_proof_buffer(std::vector<uint8_t>&& v) {
   if (g_pb.size() < 4) g_pb.push_back(std::move(v));
 }
 namespace {
-struct EvTimer {
-  bool on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
-  std::vector<double*> dst;
-  std::vector<double> bytes;
-  hipEvent_t begin(hipStream_t st) {
-    hipEvent_t e;
-    HIP_CHECK(hipEventCreate(&e));
-    HIP_CHECK(hipEventRecord(e, st));
-    return e;
-  }
-  void end(hipEvent_t b, hipStream_t st, double* into) {
-    hipEvent_t e;
-    HIP_CHECK(hipEventCreate(&e));
-    HIP_CHECK(hipEventRecord(e, st));
-    evs.push_back({b, e});
-    dst.push_back(into);
-  }
-  void collect() {
-    for (size_t i = 0; i < evs.size(); i++) {
-      HIP_CHECK(hipEventSynchronize(evs[i].second));
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, evs[i].first, evs[i].second));
-      *dst[i] += ms;
-      HIP_CHECK(hipEventDestroy(evs[i].first));
-      HIP_CHECK(hipEventDestroy(evs[i].second));
-    }
-    evs.clear();
-    dst.clear();
-  }
-};
-
 // An asynchronous device -> host copy into a pinned buffer, waited for later by spinning on its
 // event (fetch() waits at once).  Process-global instances rely on the API lock.
 struct Mailbox {
@@ -277,33 +239,6 @@ void Round::commit(hipStream_t st, bool fetch_root) {
   for (CMat& m : mats) refs.push_back(m.ref());
   merkle_build(refs, tree, st, fetch_root);
 }
-
-namespace {
-// How one proof is split over the ranks of a shard context.  Rank k owns the
-// bit-reversed positions [k H/G, (k+1) H/G) of every vector of height H >= G * 1024 (LDEs,
-// Merkle layers, reduced openings, FRI layers): the natural rows i = r (mod G), r = bitrev_G(k).
-// Shorter vectors are replicated.
-struct Plan {
-  int G = 1, lg = 0, k = 0, r = 0;
-  int r2 = 0, k2 = 0;  // residue class of the quotient's next rows (i + 2) and its owner
-  bool on() const { return G > 1; }
-  bool sharded(size_t H) const { return G > 1 && H >= (size_t)G * SHARD_MIN_LEAVES; }
-  size_t blk(size_t H) const { return H >> lg; }
-  size_t row0(size_t H) const { return (size_t)k * blk(H); }
-};
-Plan make_plan() {
-  Plan p;
-  const ShardCtx* c = shard_ctx();
-  if (!c || c->world <= 1) return p;
-  p.G = c->world;
-  p.lg = log2i((size_t)p.G);
-  p.k = c->rank;
-  p.r = (int)bitrev32((uint32_t)p.k, p.lg);
-  p.r2 = (p.r + 2) % p.G;
-  p.k2 = (int)bitrev32((uint32_t)p.r2, p.lg);
-  return p;
-}
-}  // namespace
 
 // Columns each chip reads at the next row (verifier.cpp: next_row_columns), computed once.
 static const NextCols& chip_next_cols(int chip) {
@@ -394,7 +329,7 @@ void commit_lde(CMat& cm, const uint32_t* evals, size_t n, int w, uint32_t domai
 }
 
 // ------------------------------------------------------------------------ setup
-// The quotient-roots mailbox of each lane (the API lock is held: see open_impl's gbox).
+// The quotient-roots mailbox of each lane (the API lock is held: see pcs_open's gbox).
 static Mailbox* roots_boxes() {
   static Mailbox boxes[MAX_LANES];
   return boxes;
@@ -727,12 +662,7 @@ std::vector<uint8_t> open_impl(const ProvingKey& pk, MainData& md, Challenger ch
   // the quotient commit, and replays the same steps before sampling zeta.
   DBuf<DevChallenger> dc_d(1);
   {
-    DevChallenger dc;
-    std::memcpy(dc.st, ch.st, sizeof(dc.st));
-    std::memcpy(dc.in, ch.in, sizeof(dc.in));
-    std::memcpy(dc.out, ch.out, sizeof(dc.out));
-    dc.nin = ch.nin;
-    dc.nout = ch.nout;
+    DevChallenger dc = dev_challenger(ch);
     // fault injection for tests/test_gpu.py: a device sponge that is not the host's must end in
     // an error at proving time, not in a proof the verifier rejects
     if (opt.fault_device_challenger)
@@ -794,16 +724,7 @@ std::vector<uint8_t> open_impl(const ProvingKey& pk, MainData& md, Challenger ch
     apows[k].reset(K);
     tg.apows[k] = apows[k].p;
     tg.K[k] = K;
-    QuotParams& qp = qph[k];
-    qp.alpha_pows = apows[k].p;
-    const uint32_t three = to_mont(3);
-    const uint32_t sn = mpow(three, n);
-    qp.zh_even = msub(sn, ONE);
-    qp.zh_odd = msub(mneg(sn), ONE);
-    qp.zh_even_inv = minv(qp.zh_even);
-    qp.zh_odd_inv = minv(qp.zh_odd);
-    qp.wn_inv = minv(two_adic_gen(log2i(n)));
-    qp.shift = three;
+    qph[k] = quot_params_of_height(n, apows[k].p);
   }
   upload_async(qp_d.p, qph.data(), nc * sizeof(QuotParams), st);
   challenge_quot(dc_d.p, permr.tree.layers.back().p, cums_d.p, nc, pc_d.p, qp_d.p, tg, st);
@@ -1000,634 +921,37 @@ std::vector<uint8_t> open_impl(const ProvingKey& pk, MainData& md, Challenger ch
   };
   if (!dev_zeta) replay();
 
-  // ---- PCS open: opened values (prover.rs:417-470)
-  hipEvent_t e3 = ev.on ? ev.begin(st) : nullptr;
-  span.begin("open multi batches");  // prover.rs:460 (opened values, reduced openings, FRI, queries)
-  const Round* rounds[4] = {&pk.prep, &mainr, &permr, &quotr};
-  struct MatPts {
-    int npts;
-    EF pts[2];
-    size_t off[2];  // offsets into the opened-values buffer
-  };
-  std::vector<MatPts> mp[4];
-  int Lmax = 0;
-  size_t nvals = 0;
-  for (int r = 0; r < 4; r++) {
-    for (size_t i = 0; i < rounds[r]->mats.size(); i++) {
-      const CMat& m = rounds[r]->mats[i];
-      bool lo;
-      if (r == 0) lo = CHIP_INFO[pk.chip_of[i]].local_only;
-      else if (r == 1) lo = CHIP_INFO[chip[i]].local_only;
-      else lo = (r == 3);
-      MatPts p;
-      p.npts = lo ? 1 : 2;
-      p.pts[0] = zeta;
-      p.pts[1] = ef_mul_base(zeta, two_adic_gen(m.log_n));
-      for (int j = 0; j < p.npts; j++) {
-        p.off[j] = nvals;
-        nvals += m.lde.width;
-      }
-      mp[r].push_back(p);
-      Lmax = std::max(Lmax, m.log_n + LOG_BLOWUP);
-    }
-  }
-  // Inverse denominators 1 / (x_t - point), indexed by global LDE position.  Unsharded: one
-  // table over the tallest height for zeta (smaller heights read its prefix) and one per height
-  // for the second point.  Sharded: per height, the rank's range where the height is sharded
-  // and the whole height where it is replicated.
-  // A replicated matrix at a sharded height (the preprocessed ones) is opened over its whole
-  // low coset: that height also gets full tables (fa, fb).
-  struct Invd {
-    DBuf<EF> a, b, fa, fb;
-    size_t t0 = 0;
-    const EF* pa() const { return a.p - t0; }
-    const EF* pb() const { return b.p ? b.p - t0 : nullptr; }
-    const EF* full_a() const { return fa.p ? fa.p : a.p; }  // a is full where fa is absent
-    const EF* full_b() const { return fa.p ? fb.p : b.p; }
-  };
-  std::map<int, bool> two_at;  // LDE log heights present -> some matrix opened at two points
-  std::map<int, bool> rep_at;  // ... -> a replicated matrix is opened at that height
-  for (int r = 0; r < 4; r++)
-    for (size_t i = 0; i < rounds[r]->mats.size(); i++) {
-      const int lh = rounds[r]->mats[i].log_n + LOG_BLOWUP;
-      two_at[lh] |= mp[r][i].npts == 2;
-      rep_at[lh] |= !rounds[r]->mats[i].sharded;
-    }
-  htrace().mark("inv_denoms launch");
-  DBuf<EF> invd_zeta, w_zeta;
-  static const bool wtab_on = [] {  // BFZ_OPEN_WTAB=0: weights computed in the openings (A/B)
-    const char* e = std::getenv("BFZ_OPEN_WTAB");
-    return !(e && *e == '0');
-  }();
-  if (!plan.on()) {
-    invd_zeta.reset((size_t)1 << Lmax);
-    if (wtab_on) w_zeta.reset((size_t)1 << (Lmax - 1));
-    inv_denoms_dev(zeta_d, Lmax, invd_zeta.p, st, w_zeta.p);
-  }
-  // a sharded proof's many small opening launches (one per matrix, table and height) go out as
-  // one batch each (BFZ_OPEN_SHARD_BATCH=0: one launch per matrix / table / range, A/B)
-  static const bool sbatch = [] {
-    const char* e = std::getenv("BFZ_OPEN_SHARD_BATCH");
-    return !(e && *e == '0');
-  }();
-  std::vector<InvJob> ijobs;
-  auto inv_range = [&](const EF& z, int lh, size_t t0, size_t cnt, EF* out) {
-    if (sbatch) ijobs.push_back({z, lh, t0, cnt, out});
-    else inv_denoms_range(z, lh, t0, cnt, out, st);
-  };
-  std::map<int, Invd> invd;
-  for (const auto& [lh, two] : two_at) {
-    const size_t H = (size_t)1 << lh;
-    const bool sh = plan.sharded(H);
-    const size_t t0 = sh ? plan.row0(H) : 0, cnt = sh ? plan.blk(H) : H;
-    Invd& d = invd[lh];
-    d.t0 = t0;
-    if (plan.on()) {
-      d.a.reset(cnt);
-      inv_range(zeta, lh, t0, cnt, d.a.p);
-    } else {
-      d.a = DBuf<EF>::borrow(invd_zeta.p, H);
-    }
-    const EF znext = ef_mul_base(zeta, two_adic_gen(lh - LOG_BLOWUP));
-    if (two && plan.on()) {  // single GPU: read from the zeta table (prev2_pos, fri.hip)
-      d.b.reset(cnt);
-      inv_range(znext, lh, t0, cnt, d.b.p);
-    }
-    if (sh && rep_at[lh]) {  // the low coset only: positions [0, H / 2)
-      d.fa.reset(H / 2);
-      inv_range(zeta, lh, 0, H / 2, d.fa.p);
-      if (two) {
-        d.fb.reset(H / 2);
-        inv_range(znext, lh, 0, H / 2, d.fb.p);
-      }
-    }
-  }
-  inv_denoms_ranges(ijobs, st);
-  // Opened values.  Replicated matrices: barycentric over the low coset of the LDE.  Sharded
-  // matrices: the rank's 1/G slice of sum_j c_j (z / s)^j (s = the trace domain's shift) from
-  // the kept coefficients; the slices are summed across ranks below.
-  DBuf<EF> opened_d(nvals);
-  std::map<std::array<uint32_t, 5>, DBuf<EF>> ptabs;  // (point, log n) -> powers on the range
-  std::vector<PowJob> pjobs;
-  auto ptable = [&](const EF& z, int log_n, size_t j0, size_t len) {
-    const std::array<uint32_t, 5> key{z.c[0], z.c[1], z.c[2], z.c[3], (uint32_t)log_n};
-    auto it = ptabs.find(key);
-    if (it != ptabs.end()) return (const EF*)it->second.p;
-    DBuf<EF> t(len);
-    if (sbatch) pjobs.push_back({z, j0, len, t.p});
-    else pow_table(z, j0, len, t.p, st);
-    const EF* p = t.p;
-    ptabs.emplace(key, std::move(t));
-    return p;
-  };
-  // Unsharded: the openings run in three transcript-ordered groups (preprocessed + main rounds,
-  // the permutation round, the quotient round), each copied to the host as soon as it is done,
-  // so the host observes a group (~250 host permutations in all) while the GPU computes the
-  // next one instead of after all of them.
-  const bool grouped = !plan.on();
-  auto group_of = [&](int r) { return !grouped ? 0 : r <= 1 ? 0 : r - 1; };
-  constexpr int NGROUP = 3;
-  std::vector<OpenDesc> open1g[NGROUP], open2g[NGROUP];
-  size_t gend[NGROUP] = {0, 0, 0};  // end of each group's range in the opened-value buffer
-  for (int r = 0; r < 4; r++)
-    for (size_t i = 0; i < rounds[r]->mats.size(); i++) {
-      const CMat& m = rounds[r]->mats[i];
-      const int lh = m.log_n + LOG_BLOWUP;
-      const bool two = mp[r][i].npts == 2;
-      EF* out_a = opened_d.p + mp[r][i].off[0];
-      EF* out_b = two ? opened_d.p + mp[r][i].off[1] : nullptr;
-      if (m.sharded) {
-        const size_t len = m.n >> plan.lg, j0 = (size_t)plan.k * len;
-        const uint32_t sinv = minv(m.shift);
-        const EF* tab[2] = {nullptr, nullptr};
-        for (int j = 0; j < mp[r][i].npts; j++)
-          tab[j] = ptable(ef_mul_base(mp[r][i].pts[j], sinv), m.log_n, j0, len);
-        const EF ninv = ef_base(minv(to_mont((uint32_t)(m.n % P))));
-        if (!sbatch) {
-          open_coefficients(m.coef.p + j0, m.n, m.lde.width, len, tab[0], ninv, out_a, tab[1],
-                            ninv, out_b, st);
-          continue;
-        }
-        OpenDesc o{};  // the coefficient form in the batched launch (fri.h)
-        o.tab = 1;
-        o.mat = m.coef.p + j0;
-        o.height = m.n;  // column stride
-        o.rows = len;
-        o.w = m.lde.width;
-        o.logH = lh;
-        o.invd_a = tab[0];
-        o.invd_b = two ? tab[1] : tab[0];
-        o.scale_a = o.scale_b = ninv;
-        o.out_a = out_a;
-        o.out_b = two ? out_b : out_a;
-        (two ? open2g : open1g)[group_of(r)].push_back(o);
-        continue;
-      }
-      const uint32_t three_n = mpow(to_mont(3), m.n);
-      const uint32_t n_f = to_mont((uint32_t)(m.n % P));
-      const Invd& d = invd.at(lh);
-      OpenDesc o{};
-      o.mat = m.lde.buf.p;
-      o.height = m.lde.height;
-      o.w = m.lde.width;
-      o.logH = lh;
-      o.invd_a = d.full_a();
-      o.invd_b = two ? d.full_b() : o.invd_a;  // nullptr: derived from the zeta table
-      // scale = (z^n - 3^n) / (3^n n), the same for both points ((zeta w_n)^n = zeta^n); with
-      // derived second-point denominators it also carries w_n^-1 (see k_reduce)
-      o.wtab = w_zeta.p;  // unsharded: the weight table (nullptr: weights computed per row)
-      const uint32_t zb = two && !o.invd_b && !o.wtab ? minv(two_adic_gen(m.log_n)) : ONE;
-      if (dev_zeta) {  // computed by k_open_final_batch from the device's zeta
-        o.zeta = zeta_d;
-        o.zlog = m.log_n;
-        o.z3n = three_n;
-        o.zc = minv(mmul(three_n, n_f));
-        o.zb = zb;
-      } else {
-        const EF zn = ef_pow(zeta, m.n);
-        o.scale_a = ef_mul_base(ef_sub(zn, ef_base(three_n)), minv(mmul(three_n, n_f)));
-        o.scale_b = ef_mul_base(o.scale_a, zb);
-      }
-      o.out_a = out_a;
-      o.out_b = two ? out_b : out_a;
-      (two ? open2g : open1g)[group_of(r)].push_back(o);
-    }
-  pow_tables(pjobs, st);  // before the opening batches that read them (same stream)
-  for (int r = 0; r < 4; r++)
-    if (!mp[r].empty()) {
-      const MatPts& last = mp[r].back();
-      gend[group_of(r)] = std::max(gend[group_of(r)], last.off[last.npts - 1] +
-                                                          rounds[r]->mats.back().lde.width);
-    }
-  std::vector<EF> opened(nvals);
-  // gev / gbox (and tbox below) belong to this proof's lane and are reallocated on the
-  // assumption that no copy into them is pending: safe only because every caller holds the API
-  // lock (one proof per lane at a time) and every proof synchronizes before it returns.  A
-  // caller outside the lock is a bug.
-  if (api_lock_depth() == 0) throw std::logic_error("open_impl called outside the bfz API lock");
-  static_assert(NGROUP <= Lane::NGEV, "lane events");
-  Lane& ln = lane();
-  hipEvent_t* gev = ln.gev;
-  if (grouped) {
-    if (!gev[0])
-      for (int g = 0; g < NGROUP; g++) HIP_CHECK(hipEventCreateWithFlags(&gev[g], hipEventDisableTiming));
-    if (nvals > ln.gcap) {  // no copy into it is pending: every proof waits for its groups
-      if (ln.gbox) HIP_CHECK(hipHostFree(ln.gbox));
-      ln.gcap = std::max(nvals, (size_t)1024);
-      HIP_CHECK(hipHostMalloc(&ln.gbox, ln.gcap * sizeof(EF), hipHostMallocDefault));
-    }
-  }
-  EF* gbox = static_cast<EF*>(ln.gbox);
-  for (int g = 0; g < (grouped ? NGROUP : 1); g++) {
-    open_batch(open2g[g], 2, st);  // barycentric openings: two partial + two final launches
-    open_batch(open1g[g], 1, st);
-    if (!grouped) break;
-    const size_t b0 = g ? gend[g - 1] : 0, b1 = std::max(gend[g], b0);
-    if (b1 > b0)
-      HIP_CHECK(hipMemcpyAsync(gbox + b0, opened_d.p + b0, (b1 - b0) * sizeof(EF),
-                               hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipEventRecord(gev[g], st));
-  }
-  // ---- reduced-opening descriptors (TwoAdicFriPcs::open, prover.rs:460-470), built while the
-  // openings run: per LDE height, every column of every matrix opened there in round order; the
-  // alpha-dependent parts (column coefficients alpha^k, the matrices' alpha^w, the job's ya / yb)
-  // are filled by reduce_prep on the device once alpha is known, so the host's work after the
-  // last opened value is observing it and sampling alpha.
-  struct RedJob {
-    int lh;
-    size_t col0, mat0, ncols;
-    int nmats;
-    bool has_b;
-  };
-  std::vector<RedCol> red_cols;
-  std::vector<RedMat> red_mats;
-  std::vector<RedJob> red_jobs;
-  std::vector<RedColPrep> col_prep;
-  std::vector<RedMatPrep> mat_prep;
-  std::vector<RedJobPrep> job_prep;
-  for (int lh = Lmax; lh >= 1; lh--) {
-    const size_t col0 = red_cols.size(), mat0 = red_mats.size();
-    uint32_t e = 0;  // the reduction order: point a's columns, then point b's, matrix by matrix
-    bool has_b = false;
-    for (int r = 0; r < 4; r++)
-      for (size_t i = 0; i < rounds[r]->mats.size(); i++) {
-        const CMat& m = rounds[r]->mats[i];
-        if (m.log_n + LOG_BLOWUP != lh) continue;
-        const int w = m.lde.width;
-        const bool two = mp[r][i].npts == 2;
-        RedMat rm{};
-        rm.first = (int)(red_cols.size() - col0);
-        rm.count = w;
-        rm.has_b = two ? 1 : 0;
-        for (int c = 0; c < w; c++) {
-          RedCol rc{};
-          rc.col = m.rows() + (size_t)c * m.stride();
-          red_cols.push_back(rc);
-          col_prep.push_back({e + (uint32_t)c, (uint32_t)(mp[r][i].off[0] + c),
-                              two ? (uint32_t)(mp[r][i].off[1] + c) : 0xffffffffu, (uint32_t)w});
-        }
-        // the second point's coefficients are the first point's times alpha^w; single GPU: its
-        // denominators come from the zeta table times w_n^-1 (reduce_range), folded into kb / yb
-        mat_prep.push_back({(uint32_t)w, two && !plan.on() ? minv(two_adic_gen(m.log_n)) : ONE});
-        red_mats.push_back(rm);
-        e += (uint32_t)(mp[r][i].npts * w);
-        has_b |= two;
-      }
-    if (red_cols.size() == col0) continue;
-    const size_t ncols = red_cols.size() - col0, nm = red_mats.size() - mat0;
-    red_jobs.push_back({lh, col0, mat0, ncols, (int)nm, has_b});
-    RedJobPrep jp{};
-    jp.col0 = (uint32_t)col0;
-    jp.ncols = (uint32_t)ncols;
-    jp.mat0 = (uint32_t)mat0;
-    jp.nmats = (uint32_t)nm;
-    jp.yb_fold = has_b && !plan.on() ? minv(two_adic_gen(lh - LOG_BLOWUP)) : ONE;
-    job_prep.push_back(jp);
-  }
-  DBuf<RedCol> red_cols_d(std::max<size_t>(red_cols.size(), 1));
-  DBuf<RedMat> red_mats_d(std::max<size_t>(red_mats.size(), 1));
-  DBuf<RedColPrep> col_prep_d(std::max<size_t>(col_prep.size(), 1));
-  DBuf<RedMatPrep> mat_prep_d(std::max<size_t>(mat_prep.size(), 1));
-  DBuf<RedJobPrep> job_prep_d(std::max<size_t>(job_prep.size(), 1));
-  upload_async(red_cols_d.p, red_cols.data(), red_cols.size() * sizeof(RedCol), st);
-  upload_async(red_mats_d.p, red_mats.data(), red_mats.size() * sizeof(RedMat), st);
-  upload_async(col_prep_d.p, col_prep.data(), col_prep.size() * sizeof(RedColPrep), st);
-  upload_async(mat_prep_d.p, mat_prep.data(), mat_prep.size() * sizeof(RedMatPrep), st);
-  upload_async(job_prep_d.p, job_prep.data(), job_prep.size() * sizeof(RedJobPrep), st);
-  htrace().mark("reduce descriptors");
-
-  if (dev_zeta) replay();  // the openings are queued: now the host's transcript catches up
-  if (plan.on()) {  // one all-gather; sharded matrices' slices summed, replicated ones kept
-    DBuf<EF> all(nvals * plan.G);
-    coll_sync(st);
-    htrace().mark("sharded openings done");
-    shard->allgather(opened_d.p, nvals * sizeof(EF), all.p);
-    std::vector<EF> h(nvals * plan.G);
-    HIP_CHECK(hipMemcpyAsync(h.data(), all.p, h.size() * sizeof(EF), hipMemcpyDeviceToHost, st));
-    coll_sync(st);
-    htrace().mark("sharded openings on host");
-    for (int r = 0; r < 4; r++)
-      for (size_t i = 0; i < rounds[r]->mats.size(); i++) {
-        const CMat& m = rounds[r]->mats[i];
-        for (int j = 0; j < mp[r][i].npts; j++)
-          for (int c = 0; c < m.lde.width; c++) {
-            const size_t o = mp[r][i].off[j] + c;
-            EF v = h[(size_t)plan.k * nvals + o];
-            if (m.sharded) {
-              v = ef_zero();
-              for (int g = 0; g < plan.G; g++) v = ef_add(v, h[(size_t)g * nvals + o]);
-            }
-            opened[o] = v;
-          }
-      }
-  }
-  // the opened values reduce_prep reads: the openings' own buffer (single GPU) or, sharded, the
-  // rank-summed values assembled above
-  DBuf<EF> opened_sum_d;
-  const EF* opened_dev = opened_d.p;
-  if (plan.on()) {
-    opened_sum_d.reset(std::max<size_t>(nvals, 1));
-    upload_async(opened_sum_d.p, opened.data(), nvals * sizeof(EF), st);
-    opened_dev = opened_sum_d.p;
-  }
-  auto wait_group = [&](int g) {  // the group's values in `opened`
-    for (;;) {
-      const hipError_t e = hipEventQuery(gev[g]);
-      if (e == hipSuccess) break;
-      if (e != hipErrorNotReady) HIP_CHECK(e);
-    }
-    const size_t b0 = g ? gend[g - 1] : 0, b1 = std::max(gend[g], b0);
-    std::copy(gbox + b0, gbox + b1, opened.begin() + b0);
-  };
-  if (grouped) {
-    int have = -1;  // groups copied into `opened` so far
-    for (int r = 0; r < 4; r++) {
-      while (have < group_of(r)) wait_group(++have);
-      if (opt.observe_openings)  // decision D1: opened values enter the transcript
-        for (size_t i = 0; i < rounds[r]->mats.size(); i++)
-          for (int j = 0; j < mp[r][i].npts; j++)
-            for (int c = 0; c < rounds[r]->mats[i].lde.width; c++)
-              ch.observe_ef(opened[mp[r][i].off[j] + c]);
-    }
-    while (have < NGROUP - 1) wait_group(++have);
-    htrace().mark("opened observed");
-  } else if (opt.observe_openings) {
-    htrace().mark("opened summed");
-    for (int r = 0; r < 4; r++)
-      for (size_t i = 0; i < rounds[r]->mats.size(); i++)
-        for (int j = 0; j < mp[r][i].npts; j++)
-          for (int c = 0; c < rounds[r]->mats[i].lde.width; c++)
-            ch.observe_ef(opened[mp[r][i].off[j] + c]);
-  }
-  const EF fri_alpha = ch.sample_ef();
-  htrace().mark("fri alpha");
-
-  // ---- reduced openings: the alpha-dependent coefficients of the descriptors built above, then
-  // one k_reduce launch per LDE height
-  DBuf<EF> alpha_yab(1 + 2 * std::max<size_t>(red_jobs.size(), 1));  // alpha, then {ya, yb} per job
-  upload_async(alpha_yab.p, &fri_alpha, sizeof(EF), st);
-  reduce_prep(red_cols_d.p, col_prep_d.p, red_mats_d.p, mat_prep_d.p, job_prep_d.p,
-              (int)red_jobs.size(), opened_dev, alpha_yab.p, alpha_yab.p + 1, st);
-  std::map<int, DBuf<EF>> ro;
-  for (size_t ji = 0; ji < red_jobs.size(); ji++) {
-    const RedJob& j = red_jobs[ji];
-    const size_t H = (size_t)1 << j.lh;
-    const bool sh = plan.sharded(H);
-    const size_t t0 = sh ? plan.row0(H) : 0, cnt = sh ? plan.blk(H) : H;
-    DBuf<EF> r(cnt);
-    const Invd& d = invd.at(j.lh);
-    reduce_range(red_cols_d.p + j.col0, red_mats_d.p + j.mat0, j.nmats, H, t0, cnt, d.pa(),
-                 j.has_b ? d.pb() : nullptr, alpha_yab.p + 1 + 2 * ji, j.has_b, r.p - t0, st,
-                 (int)j.ncols);
-    ro.emplace(j.lh, std::move(r));
-  }
-  if (ev.on) ev.end(e3, st, &tms->open);
-
-  // ---- FRI commit phase (fri::prover::commit_phase)
-  hipEvent_t e4 = ev.on ? ev.begin(st) : nullptr;
-  // A layer of a sharded proof stays row-sharded (values [e0, e0 + len / G)) while its fold
-  // output has >= G * 1024 values; the first shorter one is all-gathered and the rest is
-  // computed by every rank.
-  struct FriLayer {
-    DBuf<EF> v;
-    size_t e0 = 0;
-    bool local = false;
-  };
-  std::vector<FriLayer> layers;
-  std::vector<MerkleTree> trees;
+  // ---- PCS open (prover.rs:417-470): opened values, reduced openings, FRI, queries (pcs_open.hip)
+  PcsOpenIn oin;
   {
-    const size_t H = (size_t)1 << Lmax;
-    layers.push_back({std::move(ro.at(Lmax)), plan.sharded(H) ? plan.row0(H) : 0, plan.sharded(H)});
-  }
-  ro.erase(Lmax);
-  // The transcript steps of the rounds run on the device (fri_challenge): the input buffer is
-  // empty here (fri_alpha was just sampled), so each round is observe(root) -> one duplex ->
-  // beta = 4 pops, and no host round trip is needed until the final polynomial.
-  if (ch.nin != 0) throw std::runtime_error("FRI: unexpected pending challenger input");
-  DBuf<uint32_t> dstate(16);
-  upload_async(dstate.p, ch.st, 64, st);
-  const int nrounds = Lmax - LOG_BLOWUP;
-  DBuf<EF> betas(std::max(nrounds, 1));
-  size_t len = (size_t)1 << Lmax;
-  // Every sharded round costs one subtree-root all-gather: rounds stay sharded only while
-  // h >= FRI_SHARD_MIN and the shorter tail (a few hundred thousand permutations) runs on every
-  // rank after one all-gather of the layer.
-  // (BFZ_FRI_SHARD_MIN overrides it: the tests shard small proofs' rounds too)
-  static const size_t FRI_SHARD_MIN = [] {
-    const char* e = std::getenv("BFZ_FRI_SHARD_MIN");
-    return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)1 << 18;
-  }();
-  auto fri_sharded = [&](size_t h) { return plan.sharded(h) && h >= FRI_SHARD_MIN; };
-  auto gather = [&](DBuf<EF>& v, size_t len) {  // a row-sharded vector of len values, in place
-    DBuf<EF> all(len);
-    coll_sync(st);
-    shard->allgather(v.p, plan.blk(len) * sizeof(EF), all.p);
-    v = std::move(all);
-  };
-  DBuf<uint32_t> tail_trees;  // the tail rounds' trees and layers (views below borrow them)
-  DBuf<EF> tail_layers;
-  // A replicated round's fold is left pending and runs fused with the next round's leaf hashes
-  // (fri_fold_leaves): layers.back() is then allocated but not yet written.
-  struct PendingFold {
-    const EF* in = nullptr;
-    const EF* beta = nullptr;
-    const EF* add = nullptr;
-    size_t n = 0;  // fold outputs
-  } pend;
-  auto flush_fold = [&]() {
-    if (!pend.in) return;
-    fri_fold_range(pend.in, layers.back().v.p, pend.n, 0, pend.n, pend.beta, pend.add, st);
-    pend = PendingFold{};
-  };
-  for (int rd = 0; len > ((size_t)1 << LOG_BLOWUP); rd++) {
-    const size_t h = len / 2;
-    FriLayer& cur = layers.back();
-    if (!cur.local && h <= (size_t)FRI_TAIL_MAXH) {  // every remaining round in one launch
-      flush_fold();
-      FriTailRounds a;
-      a.logh0 = log2i(h);
-      a.nr = log2i(len) - LOG_BLOWUP;
-      a.in = cur.v.p;
-      a.state = dstate.p;
-      a.beta = betas.p + rd;
-      size_t nw = 0, nv = 0;
-      for (int r = 0; r < a.nr; r++) {
-        nw += 8 * ((h >> r) * 2 - 1);
-        nv += h >> r;
+    const Round* rounds[4] = {&pk.prep, &mainr, &permr, &quotr};
+    const int group[4] = {0, 0, 1, 2};  // preprocessed + main, permutation, quotient
+    for (int r = 0; r < 4; r++) {
+      PcsRound pr{rounds[r], group[r], {}};
+      for (size_t i = 0; i < rounds[r]->mats.size(); i++) {
+        bool local_only = r == 3;  // the quotient chunks are opened at zeta alone
+        if (r == 0) local_only = CHIP_INFO[pk.chip_of[i]].local_only;
+        if (r == 1) local_only = CHIP_INFO[chip[i]].local_only;
+        pr.two.push_back(local_only ? 0 : 1);
       }
-      tail_trees.reset(nw);
-      tail_layers.reset(nv);
-      nw = nv = 0;
-      for (int r = 0; r < a.nr; r++) {
-        const size_t hr = h >> r;
-        const EF* rows = r ? tail_layers.p + nv - 2 * hr : cur.v.p;
-        trees.emplace_back();
-        MerkleTree& t = trees.back();
-        t.mats = {MatRef{(const uint32_t*)rows, hr, 8}};
-        t.layers.resize(log2i(hr) + 1);
-        a.tree[r] = tail_trees.p + nw;
-        for (size_t L = 0; L < t.layers.size(); L++) {
-          t.layers[L] = DBuf<uint32_t>::borrow(tail_trees.p + nw, 8 * (hr >> L));
-          nw += 8 * (hr >> L);
-        }
-        a.layer[r] = tail_layers.p + nv;
-        const int lgh = log2i(hr);
-        a.add[r] = ro.count(lgh) ? ro.at(lgh).p : nullptr;
-        layers.push_back({DBuf<EF>::borrow(tail_layers.p + nv, hr), 0, false});
-        nv += hr;
-      }
-      fri_tail_rounds(a, st);
-      len = h >> (a.nr - 1);
-      break;
+      oin.rounds.push_back(std::move(pr));
     }
-    if (cur.local && !fri_sharded(h)) {
-      gather(cur.v, len);
-      cur.e0 = 0;
-      cur.local = false;
-    }
-    const bool loc = cur.local;
-    const size_t i0 = loc ? plan.row0(h) : 0, cnt = loc ? plan.blk(h) : h;
-    trees.emplace_back();
-    MerkleTree& t = trees.back();
-    std::function<void(size_t, size_t, uint32_t*)> fused;
-    if (pend.in) {  // this round's layer is the pending fold's output: fold + hash in one pass
-      const PendingFold pf = pend;
-      EF* out = cur.v.p;
-      fused = [pf, out, h, &st](size_t, size_t, uint32_t* dig) {
-        fri_fold_leaves(pf.in, out, h, pf.beta, pf.add, dig, st);
-      };
-      pend = PendingFold{};
-    }
-    merkle_from_rows8(t, (const uint32_t*)(cur.v.p - 2 * i0), h, st, /*fetch_root=*/false,
-                      RootChallenge{dstate.p, betas.p + rd}, /*allow_shard=*/loc, fused);
-    DBuf<EF> next(cnt);
-    const int lgh = log2i(h);
-    if (!loc && ro.count(lgh) && plan.sharded(h)) gather(ro.at(lgh), h);  // replicated tail
-    const EF* add = ro.count(lgh) ? ro.at(lgh).p : nullptr;  // same range as next
-    if (!loc && h / 2 >= FRI_FUSE_MIN) pend = PendingFold{cur.v.p, betas.p + rd, add, h};
-    else fri_fold_range(cur.v.p, next.p, h, i0, cnt, betas.p + rd, add, st);
-    layers.push_back({std::move(next), i0, loc});
-    len = h;
   }
-  flush_fold();
-  const int nt = (int)trees.size();
-  if (nt > MAX_FRI_ROUNDS) throw std::runtime_error("FRI: too many rounds");
-  const int nq = opt.num_queries;
-
-  // ---- query openings: every opened word in proof order
-  // Opening segments in serialization order (same for every query; see GatherSeg).
-  auto owner_shift = [](const MerkleTree& t, int L) {  // layer L of a sharded tree
-    const int nl = (int)t.layers.size() - 1;
-    return L < t.sharded_below ? nl - L - t.shard_log : -1;
-  };
-  std::vector<GatherSeg> segs;
-  const int ncommit = nt;
-  // The segments follow the serialized query layout, its length words included as literal
-  // segments (base == nullptr: count words of value xr), so the gathered words are the query
-  // section of the proof as is.
-  auto lit = [&](uint32_t v) { segs.push_back({nullptr, 0, 0, v, 0, 1, -1, 0}); };
-  lit(4);
-  for (int r = 0; r < 4; r++) {
-    const Round& R = *rounds[r];
-    const int lrm = (int)R.tree.layers.size() - 1;
-    lit((uint32_t)R.mats.size());
-    for (const CMat& m : R.mats) {  // row (index >> (Lmax - lh)) of every column
-      const int lh = log2i(m.lde.height);
-      lit((uint32_t)m.lde.width);
-      segs.push_back({m.rows(), (uint64_t)m.stride(), (uint32_t)(Lmax - lh), 0, 1,
-                      (uint32_t)m.lde.width, m.sharded ? lh - plan.lg : -1, 0});
-    }
-    lit((uint32_t)lrm);
-    for (int L = 0; L < lrm; L++)  // sibling digest at layer L
-      segs.push_back({R.tree.layers[L].p, 1, (uint32_t)(Lmax - lrm + L), 1, 8, 8,
-                      owner_shift(R.tree, L), 0});
-  }
-  lit((uint32_t)ncommit);
-  for (int i = 0; i < ncommit; i++) {
-    const FriLayer& fl = layers[i];  // sibling EF
-    segs.push_back({(const uint32_t*)(fl.v.p - fl.e0), 1, (uint32_t)i, 1, 4, 4,
-                    fl.local ? Lmax - i - plan.lg : -1, 0});
-    const int lm = (int)trees[i].layers.size() - 1;
-    lit((uint32_t)lm);
-    for (int L = 0; L < lm; L++)
-      segs.push_back({trees[i].layers[L].p, 1, (uint32_t)(i + 1 + L), 1, 8, 8,
-                      owner_shift(trees[i], L), 0});
-  }
-  const size_t nwords = query_words(segs) * (size_t)nq;
-
-  // ---- the transcript tail on the device: observe the final constant, grind, sample the
-  // query indices (fri_transcript_tail), then the gather; one device-to-host copy returns the
-  // commit-phase roots, the final layer, the challenger, the witness and the query words.
-  // tail = [roots (8 MAX_FRI_ROUNDS) | FRI state (16) | final layer (8) | challenger | witness,
-  //         ok | qidx (nq) | query words]
-  constexpr size_t T_CH = 8 * MAX_FRI_ROUNDS + 16 + 8;
-  constexpr size_t T_RES = T_CH + sizeof(DevChallenger) / 4;
-  constexpr size_t T_Q = T_RES + 2;
-  static_assert(sizeof(DevChallenger) % 4 == 0, "DevChallenger: whole words");
-  const size_t T_W = T_Q + (size_t)nq, tail_n = T_W + nwords;
-  DBuf<uint32_t> tailbuf(tail_n);
-  DevChallenger* dch = reinterpret_cast<DevChallenger*>(tailbuf.p + T_CH);
-  if (!nt) {  // no commit-phase round: the host challenger as it stands
-    DevChallenger hc;
-    std::memcpy(hc.st, ch.st, 64);
-    std::memcpy(hc.in, ch.in, 32);
-    std::memcpy(hc.out, ch.out, 32);
-    hc.nin = ch.nin;
-    hc.nout = ch.nout;
-    upload_async(dch, &hc, sizeof(hc), st);
-  }
-  FriTail tail{};
-  for (int i = 0; i < nt; i++) tail.root[i] = trees[i].layers.back().p;
-  tail.nroots = nt;
-  tail.state = dstate.p;
-  tail.fin = layers.back().v.p;
-  hipLaunchKernelGGL(k_pack_fri_tail, dim3(1), dim3(256), 0, st, tail, tailbuf.p);
-  KCHECK();
-  htrace().mark("grind");
-  fri_transcript_tail(dch, nt ? dstate.p : nullptr, layers.back().v.p, POW_BITS, nq, Lmax,
-                      tailbuf.p + T_Q, tailbuf.p + T_RES, st);
-  gather_queries(segs, tailbuf.p + T_Q, nq, tailbuf.p + T_W, shard, st);
-  Lane& tl = lane();  // pinned: the tail of the proof (per lane)
-  if (tail_n > tl.tcap) {  // no copy into it is pending: every proof waits for its tail
-    if (tl.tbox) HIP_CHECK(hipHostFree(tl.tbox));
-    tl.tcap = tail_n + tail_n / 4;
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&tl.tbox), tl.tcap * 4, hipHostMallocDefault));
-  }
-  uint32_t* tbox = tl.tbox;
-  HIP_CHECK(hipMemcpyAsync(tbox, tailbuf.p, tail_n * 4, hipMemcpyDeviceToHost, st));
-  spin_sync(st);
-  htrace().mark("queries gathered");
-  for (int i = 0; i < nt; i++) std::memcpy(trees[i].root, &tbox[8 * i], 32);
-  EF fin[2];
-  std::memcpy(fin, &tbox[8 * MAX_FRI_ROUNDS + 16], sizeof(fin));
-  if (!ef_eq(fin[0], fin[1]) && !(shard && shard->solo))
-    throw std::runtime_error("FRI: final polynomial is not constant (trace violates the AIR)");
-  const uint32_t witness = tbox[T_RES];
-  if (tbox[T_RES + 1] != 1) throw std::runtime_error("grind: bad witness");
-  {  // The host replays the device's FRI transcript (fri::prover: observe each commit-phase
-     // root, sample its beta; observe the final constant; the witness check; the query indices)
-     // and must arrive at the device's challenger and the device's query indices.
-    for (int i = 0; i < nt; i++) {
-      ch.observe_digest(trees[i].root);
-      (void)ch.sample_ef();
-    }
-    ch.observe_ef(fin[0]);
-    if (!ch.check_witness(POW_BITS, witness))
-      throw std::runtime_error("device transcript diverged from the host challenger: PoW witness");
-    for (int q = 0; q < nq; q++)
-      if (ch.sample_bits(Lmax) != tbox[T_Q + q])
-        throw std::runtime_error("device transcript diverged from the host challenger: query index");
-    DevChallenger dc;
-    std::memcpy(&dc, &tbox[T_CH], sizeof(dc));
-    if (std::memcmp(ch.st, dc.st, 64) != 0 || ch.nin != (int)dc.nin || ch.nout != (int)dc.nout ||
-        std::memcmp(ch.in, dc.in, 4 * (size_t)ch.nin) != 0 ||
-        std::memcmp(ch.out, dc.out, 4 * (size_t)ch.nout) != 0)
-      throw std::runtime_error("device transcript diverged from the host challenger: final state");
-  }
+  oin.zeta_d = zeta_d;
+  if (dev_zeta) oin.replay = replay;  // the host's transcript catches up once the openings are queued
+  else oin.zeta = zeta;
+  oin.plan = plan;
+  oin.shard = shard;
+  oin.observe_openings = opt.observe_openings;
+  oin.num_queries = opt.num_queries;
+  oin.ev = &ev;
+  oin.tms = tms;
+  const PcsOpenOut po = pcs_open(oin, ch);
   if (after) *after = ch;  // the transcript is complete: MachineProver::open's &mut challenger
-  const uint32_t* words = tbox + T_W;
-  if (ev.on) ev.end(e4, st, &tms->fri);
-  span.end();
+  const std::vector<EF>& opened = po.opened;
+  const std::vector<std::vector<PcsOpenOut::MatPts>>& mp = po.mp;
+  const int ncommit = (int)po.commit_roots.size(), nq = opt.num_queries;
+  const size_t nwords = po.nwords;
 
   // ---- serialize (BFZ1 normal form)
   Writer w;
@@ -1675,11 +999,11 @@ std::vector<uint8_t> open_impl(const ProvingKey& pk, MainData& md, Challenger ch
     w.ef(cums[k]);
   }
   w.u32((uint32_t)ncommit);
-  for (int i = 0; i < ncommit; i++) w.digest(trees[i].root);
+  for (int i = 0; i < ncommit; i++) w.digest(po.commit_roots[i].data());
   w.u32((uint32_t)nq);
-  w.raw(words, nwords);  // every query in serialized form (canonical words + length words)
-  w.ef(fin[0]);
-  w.u32(witness);
+  w.raw(po.words, nwords);  // every query in serialized form (canonical words + length words)
+  w.ef(po.final_poly);
+  w.u32(po.pow_witness);
   htrace().mark("serialized");
   return w.take();
 }
@@ -1734,8 +1058,5 @@ std::vector<uint8_t> prove(const ProvingKey& pk, const uint8_t* in, size_t nin,
   if (cycles) *cycles = h.global_clk;
   return prove_events(pk, ev, opt, times);
 }
-
-// kernels a proof launches (gpu.h PreloadKernels)
-static PreloadKernels preload_prover{(const void*)&k_pack_fri_tail};
 
 }  // namespace bfz

@@ -15,6 +15,21 @@ struct QuotParams {
   uint32_t wn_inv;  // w_n^-1
   uint32_t shift;   // GENERATOR = 3
 };
+// The challenge-independent fields for a trace of n rows (quotient domain 3 H_2n); the rest zero.
+inline QuotParams quot_params_of_height(size_t n, const kb::EF* alpha_pows) {
+  using namespace kb;
+  QuotParams qp{};
+  qp.alpha_pows = alpha_pows;
+  const uint32_t three = to_mont(3);
+  const uint32_t sn = mpow(three, n);
+  qp.zh_even = msub(sn, ONE);
+  qp.zh_odd = msub(mneg(sn), ONE);
+  qp.zh_even_inv = minv(qp.zh_even);
+  qp.zh_odd_inv = minv(qp.zh_odd);
+  qp.wn_inv = minv(two_adic_gen(log2i(n)));
+  qp.shift = three;
+  return qp;
+}
 
 // Number of constraints (AIR + LogUp) emitted by a chip's eval.
 int num_constraints(int chip);
