@@ -470,6 +470,14 @@ extern "C" {
                               len: usize, field_repr: c_int) -> c_int;
 
     pub fn bfz_coset_lde(evals: *const u32, n: usize, w: usize, shift: u32, lde_out: *mut u32) -> c_int;
+    /// Test hooks of the NTT / LDE kernels (see bfz.h).
+    pub fn bfz_coset_lde_ex(evals: *const u32, n: usize, w: usize, src_stride: usize, src_skew: c_int,
+                            shift: u32, only_half: c_int, mode: c_int, lde_out: *mut u32) -> c_int;
+    pub fn bfz_lde_shard(evals: *const u32, n: usize, w: usize, shift: u32, log_world: c_int,
+                         rank: c_int, next_rank: c_int, next_cols: *const c_int, n_next: usize,
+                         j0: usize, len: usize, flags: c_int, coef_out: *mut u32,
+                         shard_out: *mut u32, next_out: *mut u32, dft_low_out: *mut c_int) -> c_int;
+    pub fn bfz_ntt_last_paths(mask_out: *mut u32) -> c_int;
     pub fn bfz_commit(mats: *const *const u32, heights: *const usize, widths: *const usize,
                       nmats: usize, root: *mut u32) -> c_int;
     pub fn bfz_poseidon2_permute(states: *mut u32, n: usize) -> c_int;

@@ -754,6 +754,36 @@ int bfz_verify_bincode(const char* elf, const uint32_t vk_commit[8], const uint8
                        size_t len, int field_repr);
 
 int bfz_coset_lde(const uint32_t* evals, size_t n, size_t w, uint32_t shift, uint32_t* lde_out);
+/* Test hooks of the NTT / LDE kernels (tests/test_ntt_paths_gpu.py).  Host layouts as
+ * bfz_coset_lde: row-major natural-order input in Montgomery words, row-major output in device
+ * (bit-reversed) row order.  Each call allocates its device buffers itself; every output buffer
+ * has 64 words of 0xFFFFFFFF before and after it, checked after the run (an overwritten one is an
+ * error naming the buffer), and starts as all 0xFFFFFFFF, so a word the call leaves unwritten
+ * comes back as that.
+ *
+ * bfz_coset_lde_ex: the prover's coset_lde_ex.  The source columns lie src_stride >= n words apart
+ * and src_skew (0..3) words past a 16-byte boundary; only_half 0 / 1 writes LDE rows [0, n) /
+ * [n, 2n) only, -1 both.  mode bit 0 (in place, needs only_half 0 or 1, src_stride 2n, no skew):
+ * the source is half 1 - only_half of the output buffer itself, as the quotient chunks call it.
+ * mode bit 1: heights up to 2^8 take the general three-launch path instead of the one-block kernel.
+ *
+ * bfz_lde_shard: the sharded LDE of rank `rank` of 2^log_world, through the dispatch of a sharded
+ * proof: shard_out (m x w, m = 2n / 2^log_world) = LDE rows [rank m, (rank + 1) m); next_out
+ * (m x n_next) = the rows of next_rank's block for the columns next_cols; coef_out (n x w) = n times
+ * the interpolant's coefficients, everywhere from the unfused path; the fused path stores them for
+ * [j0, j0 + len) only and leaves the inverse DFT's first-pass values in every other word (coef_out and next_out may be NULL: not fetched).  flags: bit 0 unfused, bit 1 no half-LDE kernel at two ranks, bit 2 no fused DIF
+ * stages (this call only; the BFZ_FUSED_RESIDUE, BFZ_MID_HALF, BFZ_FUSED_DIF switches are not read).
+ * *dft_low_out: the stage the fused kernel left the forward DFT at (-1: all of it), -2 = unfused.
+ *
+ * bfz_ntt_last_paths: the kernel families the calling thread's last call of either hook launched
+ * (csrc/ntt.h NTT_* bits). */
+int bfz_coset_lde_ex(const uint32_t* evals, size_t n, size_t w, size_t src_stride, int src_skew,
+                     uint32_t shift, int only_half, int mode, uint32_t* lde_out);
+int bfz_lde_shard(const uint32_t* evals, size_t n, size_t w, uint32_t shift, int log_world, int rank,
+                  int next_rank, const int* next_cols, size_t n_next, size_t j0, size_t len,
+                  int flags, uint32_t* coef_out, uint32_t* shard_out, uint32_t* next_out,
+                  int* dft_low_out);
+int bfz_ntt_last_paths(uint32_t* mask_out);
 int bfz_commit(const uint32_t* const* mats, const size_t* heights, const size_t* widths,
                size_t nmats, uint32_t root[8]);
 int bfz_poseidon2_permute(uint32_t* states, size_t n);

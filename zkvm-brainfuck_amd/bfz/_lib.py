@@ -243,6 +243,13 @@ SIGNATURES = [
                                        POINTER(POINTER(c_uint8)), POINTER(c_size_t)]),
     ("bfz_verify_bincode", c_int, [c_char_p, POINTER(c_uint32), POINTER(c_uint8), c_size_t, c_int]),
     ("bfz_coset_lde", c_int, [POINTER(c_uint32), c_size_t, c_size_t, c_uint32, POINTER(c_uint32)]),
+    ("bfz_coset_lde_ex", c_int, [POINTER(c_uint32), c_size_t, c_size_t, c_size_t, c_int, c_uint32,
+                                 c_int, c_int, POINTER(c_uint32)]),
+    ("bfz_lde_shard", c_int, [POINTER(c_uint32), c_size_t, c_size_t, c_uint32, c_int, c_int, c_int,
+                              POINTER(c_int), c_size_t, c_size_t, c_size_t, c_int,
+                              POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
+                              POINTER(c_int)]),
+    ("bfz_ntt_last_paths", c_int, [POINTER(c_uint32)]),
     ("bfz_commit", c_int, [POINTER(POINTER(c_uint32)), POINTER(c_size_t), POINTER(c_size_t),
                            c_size_t, POINTER(c_uint32)]),
     ("bfz_poseidon2_permute", c_int, [POINTER(c_uint32), c_size_t]),

@@ -1916,6 +1916,119 @@ int bfz_coset_lde(const uint32_t* evals, size_t n, size_t w, uint32_t shift, uin
   });
 }
 
+namespace {
+// A device output buffer of the NTT test hooks: `words` words with CANARY words before and after,
+// every word 0xFFFFFFFF (no field word: p < 2^31) until a kernel writes it.
+constexpr size_t CANARY = 64;
+struct GuardedBuf {
+  bfz::DBuf<uint32_t> d;
+  size_t words;
+  const char* name;
+  GuardedBuf(size_t words_, const char* name_, hipStream_t st)
+      : d(words_ + 2 * CANARY), words(words_), name(name_) {
+    HIP_CHECK(hipMemsetAsync(d.p, 0xff, (words + 2 * CANARY) * 4, st));
+  }
+  uint32_t* p() { return d.p + CANARY; }
+  void check(hipStream_t st) {  // throws if a canary word changed
+    uint32_t h[2 * CANARY];
+    HIP_CHECK(hipMemcpyAsync(h, d.p, CANARY * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(h + CANARY, d.p + CANARY + words, CANARY * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (size_t i = 0; i < 2 * CANARY; i++)
+      if (h[i] != 0xffffffffu)
+        throw std::runtime_error(std::string("canary overwritten ") +
+                                 (i < CANARY ? "before " : "after ") + name);
+  }
+};
+// Column-major (H x w) device words -> row-major host words.
+void fetch_rowmajor(const uint32_t* colmajor, size_t H, size_t w, uint32_t* host, hipStream_t st) {
+  if (H * w == 0) return;
+  bfz::DBuf<uint32_t> back(H * w);
+  bfz::transpose_to_rowmajor(colmajor, H, (int)w, back.p, st);
+  HIP_CHECK(hipMemcpyAsync(host, back.p, H * w * 4, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+}
+thread_local uint32_t g_ntt_paths = 0;
+}  // namespace
+
+int bfz_coset_lde_ex(const uint32_t* evals, size_t n, size_t w, size_t src_stride, int src_skew,
+                     uint32_t shift, int only_half, int mode, uint32_t* out) {
+  return guarded([&] {
+    const bool in_place = mode & 1;
+    if (n == 0 || (n & (n - 1))) throw std::runtime_error("height must be a power of two");
+    if (w < 1) throw std::runtime_error("at least one column");
+    if (only_half < -1 || only_half > 1) throw std::runtime_error("only_half must be -1, 0 or 1");
+    if (mode & ~3) throw std::runtime_error("mode: bit 0 in place, bit 1 no one-block kernel");
+    if (src_skew < 0 || src_skew > 3) throw std::runtime_error("src_skew must be in 0..3");
+    if (src_stride < n) throw std::runtime_error("src_stride below the height");
+    if (in_place && only_half < 0) throw std::runtime_error("in_place needs only_half 0 or 1");
+    if (in_place && (src_stride != 2 * n || src_skew))
+      throw std::runtime_error("in_place: the source is a half of the output (stride 2n, no skew)");
+    hipStream_t st = bfz::stream();
+    bfz::DBuf<uint32_t> rm(n * w), ev(n * w);
+    GuardedBuf lde(2 * n * w, "lde_out", st);
+    bfz::DBuf<uint32_t> srcbuf(in_place ? 1 : src_stride * (w - 1) + n + 4);
+    uint32_t* src = in_place ? lde.p() + (size_t)(1 - only_half) * n : srcbuf.p + src_skew;
+    HIP_CHECK(hipMemcpyAsync(rm.p, evals, n * w * 4, hipMemcpyHostToDevice, st));
+    bfz::transpose_bitrev(rm.p, n, (int)w, ev.p, st);
+    HIP_CHECK(hipMemcpy2DAsync(src, src_stride * 4, ev.p, n * 4, n * 4, w, hipMemcpyDeviceToDevice, st));
+    (void)bfz::ntt_paths_take();
+    bfz::coset_lde_ex(src, src_stride, n, (int)w, shift, lde.p(), only_half, st, mode & 2 ? 0 : -1);
+    g_ntt_paths = bfz::ntt_paths_take();
+    lde.check(st);
+    fetch_rowmajor(lde.p(), 2 * n, w, out, st);
+    return 0;
+  });
+}
+
+int bfz_lde_shard(const uint32_t* evals, size_t n, size_t w, uint32_t shift, int log_world, int rank,
+                  int next_rank, const int* next_cols, size_t n_next, size_t j0, size_t len,
+                  int flags, uint32_t* coef_out, uint32_t* shard_out, uint32_t* next_out,
+                  int* dft_low_out) {
+  return guarded([&] {
+    if (n == 0 || (n & (n - 1))) throw std::runtime_error("height must be a power of two");
+    const int L = bfz::log2i(n);
+    if (w < 1 || w > 64) throw std::runtime_error("1..64 columns");
+    if (log_world < 1 || log_world > L + 1) throw std::runtime_error("bad log_world");
+    const int G = 1 << log_world;
+    if (rank < 0 || rank >= G || next_rank < 0 || next_rank >= G)
+      throw std::runtime_error("rank outside the world");
+    if (flags & ~7) throw std::runtime_error("flags: bits 0..2");
+    if (n_next > 64) throw std::runtime_error("at most 64 next-row columns");
+    if (j0 > n || len > n - j0) throw std::runtime_error("coefficient range outside [0, n)");
+    std::vector<int> nc(next_cols, next_cols + n_next);
+    for (int c : nc)
+      if (c < 0 || c >= (int)w) throw std::runtime_error("next column outside the matrix");
+    const size_t m = (2 * n) >> log_world;
+    const int r = (int)bfz::bitrev32((uint32_t)rank, log_world);  // as make_plan
+    const int r2 = (int)bfz::bitrev32((uint32_t)next_rank, log_world);
+    hipStream_t st = bfz::stream();
+    bfz::DBuf<uint32_t> rm(n * w), ev(n * w);
+    GuardedBuf coef(n * w, "coef_out", st), shard(m * w, "shard_out", st),
+        nxt(m * n_next, "next_out", st);
+    HIP_CHECK(hipMemcpyAsync(rm.p, evals, n * w * 4, hipMemcpyHostToDevice, st));
+    bfz::transpose_bitrev(rm.p, n, (int)w, ev.p, st);
+    (void)bfz::ntt_paths_take();
+    *dft_low_out = bfz::lde_shard(ev.p, n, (int)w, coef.p(), j0, len, shift, log_world, r,
+                                  shard.p(), nc.empty() ? nullptr : &nc, r2, nxt.p(), st, flags);
+    g_ntt_paths = bfz::ntt_paths_take();
+    coef.check(st);
+    shard.check(st);
+    nxt.check(st);
+    if (coef_out) fetch_rowmajor(coef.p(), n, w, coef_out, st);
+    fetch_rowmajor(shard.p(), m, w, shard_out, st);
+    if (next_out) fetch_rowmajor(nxt.p(), m, n_next, next_out, st);
+    return 0;
+  });
+}
+
+int bfz_ntt_last_paths(uint32_t* mask_out) {
+  return guarded([&] {
+    *mask_out = g_ntt_paths;
+    return 0;
+  });
+}
+
 int bfz_commit(const uint32_t* const* mats, const size_t* heights, const size_t* widths,
                size_t nmats, uint32_t root[8]) {
   return guarded([&] {

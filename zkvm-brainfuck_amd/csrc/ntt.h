@@ -1,6 +1,7 @@
 // Device NTT / coset LDE (see ntt.hip).
 #pragma once
 #include <algorithm>
+#include <functional>
 #include <utility>
 #include <vector>
 
@@ -28,7 +29,8 @@ void coset_lde(const uint32_t* evals, size_t n, int w, uint32_t shift, uint32_t*
 // LDE rows [0, n) / [n, 2n) of each column (the other half is left untouched -- a quotient
 // chunk's own domain is that half, so the caller has its values already; -1: both halves).
 void coset_lde_ex(const uint32_t* evals, size_t src_stride, size_t n, int w, uint32_t shift,
-                  uint32_t* lde, int only_half, hipStream_t st);
+                  uint32_t* lde, int only_half, hipStream_t st, int tiny = -1);
+// tiny: heights up to 2^8 in one launch (k_lde_tiny): 1 / 0, -1 = BFZ_LDE_TINY (default on).
 
 // Sharded LDE.  lde_coefficients: coef = n * (coefficients of the interpolant
 // over H_n), natural order (the iDFT alone).  coset_residue: the rank shard of the coset LDE
@@ -43,7 +45,8 @@ void coset_residue_cols(const uint32_t* coef, size_t n, const std::vector<int>& 
                         uint32_t shift, int logG, int r, uint32_t* out, hipStream_t st);
 
 // The same in one pass over the coefficients (k_coef_fold): the iDFT's second pass keeps each
-// column's coefficients in registers, writes coef only for [j0, j0 + len) (column stride n) and
+// column's coefficients in registers, writes coef only for [j0, j0 + len) (column stride n; the
+// first pass runs into coef, so its other words are left holding that pass's intermediate) and
 // folds them into out (residue r, m x w, m = 2n / G) and, with next_cols, into nxt (residue r2,
 // the listed columns) -- natural order; residue_dft then finishes each (the forward DFT).
 // Returns false (nothing launched) where it does not apply (log n <= 14 or > 23, G > 32);
@@ -53,8 +56,32 @@ void coset_residue_cols(const uint32_t* coef, size_t n, const std::vector<int>& 
 bool coef_fold_residues(const uint32_t* evals, size_t n, int w, uint32_t* coef, size_t j0,
                         size_t len, uint32_t shift, int logG, int r, uint32_t* out,
                         const std::vector<int>* next_cols, int r2, uint32_t* nxt, int* dft_low,
-                        hipStream_t st);
+                        hipStream_t st, int ab = -1);
 void residue_dft(uint32_t* out, size_t m, int w, int dft_low, hipStream_t st);
+// ab: the A/B switches of this call as LDE_AB_* bits; -1 = the environment's (BFZ_FUSED_RESIDUE,
+// BFZ_MID_HALF, BFZ_FUSED_DIF, each on unless "0").
+enum : int { LDE_AB_UNFUSED = 1, LDE_AB_NO_MID_HALF = 2, LDE_AB_NO_FUSED_DIF = 4 };
+
+// One rank's sharded LDE, the dispatch of a sharded proof (prover.hip lde_into):
+// coef_fold_residues then residue_dft of out and nxt, else lde_coefficients then
+// coset_residue[_cols].  next_cols null or empty: no next-row residue.  *folded, if given, runs
+// between the two phases (the timed proof's event).  Returns dft_low of the fused path, -2 for
+// the unfused one.
+int lde_shard(const uint32_t* evals, size_t n, int w, uint32_t* coef, size_t j0, size_t len,
+              uint32_t shift, int logG, int r, uint32_t* out, const std::vector<int>* next_cols,
+              int r2, uint32_t* nxt, hipStream_t st, int ab = -1,
+              const std::function<void()>* folded = nullptr);
+
+// Which kernel families the calling thread has launched since the last call (test hooks).
+enum : uint32_t {
+  NTT_PASS_DIT = 1u << 0, NTT_PASS_DIF = 1u << 1, NTT_R16_DIT = 1u << 2, NTT_R16_DIF = 1u << 3,
+  NTT_TILE_DIT_DIN = 1u << 4, NTT_TILE_DIT = 1u << 5, NTT_TILE_DIF = 1u << 6,
+  NTT_LDE_TINY = 1u << 7, NTT_SCALE_SPLIT = 1u << 8, NTT_MID_FULL = 1u << 9,
+  NTT_MID_HALF = 1u << 10, NTT_MID_SHARD = 1u << 11, NTT_COEF_FOLD_R0 = 1u << 12,
+  NTT_COEF_FOLD_R2 = 1u << 13, NTT_COEF_FOLD_R3 = 1u << 14, NTT_FOLD_RESIDUE = 1u << 15,
+  NTT_TILE_B8 = 1u << 16,  // << (B - 8): the tile sizes 2^8 .. 2^14 launched
+};
+uint32_t ntt_paths_take();
 
 // Row-major natural-order host layout -> column-major bit-reversed device layout.
 void transpose_bitrev(const uint32_t* rowmajor, size_t n, int w, uint32_t* colmajor,

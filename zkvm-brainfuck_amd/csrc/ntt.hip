@@ -23,6 +23,14 @@ namespace bfz {
 using namespace kb;
 
 constexpr int TILE_LOG = 12;  // 4096 u32 per tile (16 KiB LDS)
+
+static thread_local uint32_t g_paths = 0;  // NttPath bits of this thread's launches (ntt.h)
+static inline void path(uint32_t bits) { g_paths |= bits; }
+uint32_t ntt_paths_take() {
+  const uint32_t m = g_paths;
+  g_paths = 0;
+  return m;
+}
 constexpr int CMAX = 5;       // coalesced runs of 32 elements for strided passes
 
 template <bool DIF>
@@ -786,6 +794,7 @@ static void tile_launch(dim3 grid, const uint32_t* in, size_t is, uint32_t* dst,
   const dim3 block(1 << (B - 4));
   const bool din = !DIF && ((uintptr_t)in & 15) == 0 && (is & 3) == 0;
   constexpr bool WS = B == R16_TILE_LOG;
+  path((DIF ? NTT_TILE_DIF : din ? NTT_TILE_DIT_DIN : NTT_TILE_DIT) | (NTT_TILE_B8 << (B - 8)));
   if constexpr (DIF)
     hipLaunchKernelGGL((k_ntt_tile<true, B, false, WS, WS>), grid, block, lds * 4, st, in, dst, is,
                        ds, tw);
@@ -829,12 +838,15 @@ static void r16_launch(const R16Pass& p, const uint32_t* in, size_t is, uint32_t
       (dif ? tile_dispatch<true>(p.b, grid, in, is, dst, ds, (const uint32_t*)T.fwd(), st)
            : tile_dispatch<false>(p.b, grid, in, is, dst, ds, (const uint32_t*)T.inv(), st))) {
     // specialised contiguous pass
-  } else if (dif)
+  } else if (dif) {
+    path(NTT_R16_DIF);
     hipLaunchKernelGGL(k_ntt_r16<true>, grid, dim3(threads), lds * 4, st, in, dst, is, ds, p.s0,
                        p.b, p.c, (const uint32_t*)T.fwd());
-  else
+  } else {
+    path(NTT_R16_DIT);
     hipLaunchKernelGGL(k_ntt_r16<false>, grid, dim3(threads), lds * 4, st, in, dst, is, ds, p.s0,
                        p.b, p.c, (const uint32_t*)T.inv());
+  }
   KCHECK();
   if (probe.on) probe.end(ev0, st, 8.0 * (double)((size_t)1 << L) * ncols);
 }
@@ -863,6 +875,7 @@ void ntt_passes(const uint32_t* src, uint32_t* dst, size_t src_stride, size_t ds
     dim3 grid(1u << (L - b - c), ncols);
     const uint32_t* in = first ? src : dst;
     const size_t is = first ? src_stride : dst_stride;
+    path(dif ? NTT_PASS_DIF : NTT_PASS_DIT);
     if (dif)
       hipLaunchKernelGGL(k_ntt_pass<true>, grid, dim3(256), 0, st, in, dst, is, dst_stride, s0, b,
                          c, T.fwd());
@@ -965,6 +978,7 @@ static void mid_launch(const uint32_t* coef, size_t n, int w, uint32_t shift, ui
   KernelProbe& probe = ntt_probe();
   hipEvent_t ev0 = probe.on ? probe.begin(st) : nullptr;
   const dim3 grid(1u << (L - p2.b - p2.c), ceil_div(w, MID_CPB));
+  path(mo.coef ? NTT_MID_SHARD : only_half >= 0 ? NTT_MID_HALF : NTT_MID_FULL);
 #define BFZ_MID(LL)                                                                              \
   case LL:                                                                                       \
     static_assert(MidPlan<LL>::b2 >= 4, "plan");                                                 \
@@ -988,7 +1002,7 @@ void coset_lde(const uint32_t* evals, size_t n, int w, uint32_t shift, uint32_t*
 }
 
 void coset_lde_ex(const uint32_t* evals, size_t src_stride, size_t n, int w, uint32_t shift,
-                  uint32_t* lde, int only_half, hipStream_t st) {
+                  uint32_t* lde, int only_half, hipStream_t st, int tiny) {
   const int L = log2i(n);
   // the DFT of one half: its w columns of n at stride 2n; both halves: 2w columns at stride n
   uint32_t* dft_base = only_half >= 0 ? lde + (size_t)only_half * n : lde;
@@ -1004,7 +1018,9 @@ void coset_lde_ex(const uint32_t* evals, size_t src_stride, size_t n, int w, uin
     r16_launch(plan[0], dft_base, dft_stride, dft_base, dft_stride, dft_cols, L, true, st);
     return;
   }
-  if (L >= 1 && L <= TINY_LOG_MAX && lde_tiny_on()) {  // one launch, one block per column
+  if (L >= 1 && L <= TINY_LOG_MAX && (tiny < 0 ? lde_tiny_on() : tiny != 0)) {
+    // one launch, one block per column
+    path(NTT_LDE_TINY);
     Twiddles& T = twiddles();
     T.ensure(L);
     const int B = (L + 1) / 2;
@@ -1019,6 +1035,7 @@ void coset_lde_ex(const uint32_t* evals, size_t src_stride, size_t n, int w, uin
   const int B = (L + 1) / 2;
   const uint32_t* pw = scale_tables(shift, L, B);
   dim3 grid(std::min<unsigned>(ceil_div(n, 256), 4096), w);
+  path(NTT_SCALE_SPLIT);
   hipLaunchKernelGGL(k_scale_split, grid, dim3(256), 0, st, coef.p, lde, n, B, pw, only_half);
   KCHECK();
   ntt_passes(dft_base, dft_base, dft_stride, dft_stride, dft_cols, L, /*dif=*/true, st);
@@ -1115,6 +1132,7 @@ void coset_residue_cols(const uint32_t* coef, size_t n, const std::vector<int>& 
   fp.p[0] = ONE;
   for (size_t l = 1; l < terms; l++) fp.p[l] = mmul(fp.p[l - 1], am);
   const dim3 grid(std::min<unsigned>(ceil_div(m, 256), 2048), w);
+  path(NTT_FOLD_RESIDUE);
   hipLaunchKernelGGL(k_fold_residue, grid, dim3(256), 0, st, coef, n, out, m, B, pw, map, fp);
   KCHECK();
   ntt_passes(out, out, m, m, w, log2i(m), /*dif=*/true, st);
@@ -1155,9 +1173,12 @@ static bool fused_dif_on() {  // BFZ_FUSED_DIF=0: k_coef_fold leaves the whole D
 bool coef_fold_residues(const uint32_t* evals, size_t n, int w, uint32_t* coef, size_t j0,
                         size_t len, uint32_t shift, int logG, int r, uint32_t* out,
                         const std::vector<int>* next_cols, int r2, uint32_t* nxt, int* dft_low,
-                        hipStream_t st) {
+                        hipStream_t st, int ab) {
   const int L = log2i(n);
-  if (!fused_residues_on() || L <= R16_TILE_LOG || L > 23 || logG < 1 || logG > 5 || w < 1 ||
+  const bool fused = ab < 0 ? fused_residues_on() : !(ab & LDE_AB_UNFUSED);
+  const bool mid_half = ab < 0 ? mid_half_on() : !(ab & LDE_AB_NO_MID_HALF);
+  const bool fused_dif = ab < 0 ? fused_dif_on() : !(ab & LDE_AB_NO_FUSED_DIF);
+  if (!fused || L <= R16_TILE_LOG || L > 23 || logG < 1 || logG > 5 || w < 1 ||
       w > 64)
     return false;
   Twiddles& T = twiddles();
@@ -1167,7 +1188,7 @@ bool coef_fold_residues(const uint32_t* evals, size_t n, int w, uint32_t* coef, 
   const R16Pass& p1 = plan[0];
   const R16Pass& p2 = plan[1];
   r16_launch(p1, evals, n, coef, n, w, L, false, st);
-  if (logG == 1 && !(next_cols && !next_cols->empty()) && mid_half_on()) {
+  if (logG == 1 && !(next_cols && !next_cols->empty()) && mid_half) {
     // two ranks: the residue coset is one half of the coset LDE -- k_lde_mid's half r, written
     // at stride n, with the coefficient range on the side; only the DIF tile pass is left
     mid_launch(coef, n, w, shift, out, r, MidOut{n, 0, coef, j0, len}, st);
@@ -1191,7 +1212,8 @@ bool coef_fold_residues(const uint32_t* evals, size_t n, int w, uint32_t* coef, 
   const size_t ldsz = ((size_t)1 << (p2.b + p2.c)) + ((size_t)1 << (p2.b + p2.c - 4));
   const dim3 grid(1u << (L - p2.b - p2.c), w);
   // the strided DIF stages run in the kernel for 4 and 8 ranks (R = 3, 2)
-  const int R = fused_dif_on() && (logG == 2 || logG == 3) ? 5 - logG : 0;
+  const int R = fused_dif && (logG == 2 || logG == 3) ? 5 - logG : 0;
+  path(R == 3 ? NTT_COEF_FOLD_R3 : R == 2 ? NTT_COEF_FOLD_R2 : NTT_COEF_FOLD_R0);
   const uint32_t* ti = (const uint32_t*)T.inv();
   const uint32_t* tf = (const uint32_t*)T.fwd();
 #define BFZ_CF(LL)                                                                             \
@@ -1214,6 +1236,27 @@ bool coef_fold_residues(const uint32_t* evals, size_t n, int w, uint32_t* coef, 
   KCHECK();
   *dft_low = R ? p2.s0 : -1;
   return true;
+}
+
+int lde_shard(const uint32_t* evals, size_t n, int w, uint32_t* coef, size_t j0, size_t len,
+              uint32_t shift, int logG, int r, uint32_t* out, const std::vector<int>* next_cols,
+              int r2, uint32_t* nxt, hipStream_t st, int ab, const std::function<void()>* folded) {
+  const size_t m = (2 * n) >> logG;
+  const bool nx = next_cols && !next_cols->empty();
+  // iDFT + folds in one pass over the coefficients (the fold time counts as iDFT here)
+  int dft_low = -1;
+  if (coef_fold_residues(evals, n, w, coef, j0, len, shift, logG, r, out, nx ? next_cols : nullptr,
+                         r2, nxt, &dft_low, st, ab)) {
+    if (folded) (*folded)();
+    residue_dft(out, m, w, dft_low, st);
+    if (nx) residue_dft(nxt, m, (int)next_cols->size(), dft_low, st);
+    return dft_low;
+  }
+  lde_coefficients(evals, n, w, coef, st);
+  if (folded) (*folded)();
+  coset_residue(coef, n, w, shift, logG, r, out, st);
+  if (nx) coset_residue_cols(coef, n, *next_cols, shift, logG, r2, nxt, st);
+  return -2;
 }
 
 void residue_dft(uint32_t* out, size_t m, int w, int dft_low, hipStream_t st) {

@@ -286,24 +286,14 @@ static void lde_into(CMat& cm, const uint32_t* evals, size_t n, int w, uint32_t 
       for (size_t y = 0; y < next_cols->size(); y++) cm.nmap[(*next_cols)[y]] = (uint8_t)y;
     }
     const size_t len = n >> plan->lg;  // the coefficient range this rank opens (open_ood)
-    hipEvent_t b0 = timed ? tm->begin(st) : nullptr;
-    // iDFT + folds in one pass over the coefficients (the fold time counts as iDFT here)
-    int dft_low = -1;
-    if (coef_fold_residues(evals, n, w, cm.coef.p, (size_t)plan->k * len, len, lde_shift,
-                           plan->lg, plan->r, cm.lde.buf.p, nx ? next_cols : nullptr, plan->r2,
-                           cm.nxt.p, &dft_low, st)) {
-      if (timed) tm->end(b0, st, split->idft);
-      hipEvent_t b1 = timed ? tm->begin(st) : nullptr;
-      residue_dft(cm.lde.buf.p, cm.blk, w, dft_low, st);
-      if (nx) residue_dft(cm.nxt.p, cm.blk, (int)next_cols->size(), dft_low, st);
-      if (timed) tm->end(b1, st, split->dft);
-      return;
-    }
-    lde_coefficients(evals, n, w, cm.coef.p, st);
-    if (timed) tm->end(b0, st, split->idft);
-    hipEvent_t b1 = timed ? tm->begin(st) : nullptr;
-    coset_residue(cm.coef.p, n, w, lde_shift, plan->lg, plan->r, cm.lde.buf.p, st);
-    if (nx) coset_residue_cols(cm.coef.p, n, *next_cols, lde_shift, plan->lg, plan->r2, cm.nxt.p, st);
+    hipEvent_t b0 = timed ? tm->begin(st) : nullptr, b1 = nullptr;
+    const std::function<void()> folded = [&] {  // the iDFT (and the fused folds) are queued
+      tm->end(b0, st, split->idft);
+      b1 = tm->begin(st);
+    };
+    lde_shard(evals, n, w, cm.coef.p, (size_t)plan->k * len, len, lde_shift, plan->lg, plan->r,
+              cm.lde.buf.p, nx ? next_cols : nullptr, plan->r2, cm.nxt.p, st, -1,
+              timed ? &folded : nullptr);
     if (timed) tm->end(b1, st, split->dft);
     return;
   }
