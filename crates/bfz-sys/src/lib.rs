@@ -432,6 +432,14 @@ extern "C" {
                          first_fail_per_row: *mut i32) -> c_int;
     pub fn bfz_record_uni_check(rec: *const bfz_record, chip: c_int,
                                 out: *mut bfz_uni_check_result) -> c_int;
+    /// The same checks with a failure profile per constraint: `counts[k]` rows violate constraint
+    /// `k`, the first of them is `first_rows[k]` (-1: none); K entries each.
+    pub fn bfz_uni_check_constraints(chip: c_int, trace: *const u32, height: usize, width: usize,
+                                     on_device: c_int, out_summary: *mut bfz_uni_check_result,
+                                     counts: *mut u64, first_rows: *mut i64) -> c_int;
+    pub fn bfz_record_uni_check_constraints(rec: *const bfz_record, chip: c_int,
+                                            out_summary: *mut bfz_uni_check_result,
+                                            counts: *mut u64, first_rows: *mut i64) -> c_int;
     /// `uni_stark_prove` of one chip of a device record; 1 when the record lacks the chip.
     pub fn bfz_record_uni_prove(rec: *const bfz_record, chip: c_int, ch: *mut bfz_challenger,
                                 proof: *mut *mut u8, proof_len: *mut usize,
@@ -451,6 +459,10 @@ extern "C" {
     pub fn bfz_air_check(prog: *const u8, len: usize, trace: *const u32, height: usize,
                          width: usize, on_device: c_int, out: *mut bfz_uni_check_result,
                          first_fail_per_row: *mut i32) -> c_int;
+    pub fn bfz_air_check_constraints(prog: *const u8, len: usize, trace: *const u32, height: usize,
+                                     width: usize, on_device: c_int,
+                                     out_summary: *mut bfz_uni_check_result, counts: *mut u64,
+                                     first_rows: *mut i64) -> c_int;
     pub fn bfz_air_prove(prog: *const u8, len: usize, trace: *const u32, height: usize,
                          width: usize, ch: *mut bfz_challenger, proof: *mut *mut u8,
                          proof_len: *mut usize, timings: *mut bfz_timings) -> c_int;

@@ -634,6 +634,26 @@ int bfz_uni_check(int chip, const uint32_t* trace, size_t height, size_t width, 
                   bfz_uni_check_result* out, int32_t* first_fail_per_row /* optional, natural order */);
 int bfz_record_uni_check(const bfz_record* rec, int chip, bfz_uni_check_result* out);
 
+/* The same checks without stopping at a row's first failing constraint: a failure profile per
+ * constraint, what bfz_record_debug_interactions is for the lookups.  A trace that breaks
+ * constraint 3 on every row and constraint 17 on forty rows shows both, in one run.
+ *   counts[k]      rows on which constraint k is not zero
+ *   first_rows[k]  the smallest such row, natural order; -1 if none
+ * both with K entries (the K of bfz_uni_info / bfz_air_info), indexed in emission order.
+ * out_summary is filled exactly as the matching first-fail call fills it; first_constraint is the
+ * smallest k with first_rows[k] == first_row.  Arguments, refusals, messages and return values are
+ * those of bfz_uni_check, bfz_record_uni_check (1: the record does not include the chip) and
+ * bfz_air_check (below).  on_device = 0 is the single-threaded host path (no device needed); on the
+ * device every constraint of every row is evaluated where the trace is, the tables are reduced
+ * there (per block in LDS, then atomics for the entries that are not zero) and 2K words plus the
+ * summary come back -- never a K x height matrix. */
+int bfz_uni_check_constraints(int chip, const uint32_t* trace, size_t height, size_t width,
+                              int on_device, bfz_uni_check_result* out_summary, uint64_t* counts,
+                              int64_t* first_rows);
+int bfz_record_uni_check_constraints(const bfz_record* rec, int chip,
+                                     bfz_uni_check_result* out_summary, uint64_t* counts,
+                                     int64_t* first_rows);
+
 /* uni_stark_prove (crates/core/machine/src/utils/prove.rs:97-127) of one chip of a device record:
  * the record's traces are generated on the device as bfz_record_prove does (all chips; one is
  * used) and the chip's evaluations are proven where they are -- no upload, no transpose, no copy.
@@ -713,6 +733,10 @@ int bfz_air_eval(const uint8_t* prog, size_t len, const uint32_t* local, const u
 int bfz_air_check(const uint8_t* prog, size_t len, const uint32_t* trace, size_t height,
                   size_t width, int on_device, bfz_uni_check_result* out,
                   int32_t* first_fail_per_row);
+/* bfz_uni_check_constraints (above) for a program: counts and first_rows have the program's K. */
+int bfz_air_check_constraints(const uint8_t* prog, size_t len, const uint32_t* trace, size_t height,
+                              size_t width, int on_device, bfz_uni_check_result* out_summary,
+                              uint64_t* counts, int64_t* first_rows);
 int bfz_air_prove(const uint8_t* prog, size_t len, const uint32_t* trace, size_t height,
                   size_t width, bfz_challenger* ch, uint8_t** proof, size_t* proof_len,
                   bfz_timings* timings);

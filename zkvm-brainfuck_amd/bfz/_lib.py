@@ -218,6 +218,10 @@ SIGNATURES = [
     ("bfz_uni_check", c_int, [c_int, POINTER(c_uint32), c_size_t, c_size_t, c_int,
                               POINTER(UniCheckC), POINTER(c_int32)]),
     ("bfz_record_uni_check", c_int, [c_void_p, c_int, POINTER(UniCheckC)]),
+    ("bfz_uni_check_constraints", c_int, [c_int, POINTER(c_uint32), c_size_t, c_size_t, c_int,
+                                          POINTER(UniCheckC), POINTER(c_uint64), POINTER(c_int64)]),
+    ("bfz_record_uni_check_constraints", c_int, [c_void_p, c_int, POINTER(UniCheckC),
+                                                 POINTER(c_uint64), POINTER(c_int64)]),
     ("bfz_record_uni_prove", c_int, [c_void_p, c_int, POINTER(Challenger), POINTER(POINTER(c_uint8)),
                                      POINTER(c_size_t), POINTER(Timings)]),
     ("bfz_uni_verify_batch", c_int, [POINTER(c_int), POINTER(Challenger), POINTER(POINTER(c_uint8)),
@@ -229,6 +233,9 @@ SIGNATURES = [
                              POINTER(c_uint32)]),
     ("bfz_air_check", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint32), c_size_t, c_size_t,
                               c_int, POINTER(UniCheckC), POINTER(c_int32)]),
+    ("bfz_air_check_constraints", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint32), c_size_t,
+                                          c_size_t, c_int, POINTER(UniCheckC), POINTER(c_uint64),
+                                          POINTER(c_int64)]),
     ("bfz_air_prove", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint32), c_size_t, c_size_t,
                               POINTER(Challenger), POINTER(POINTER(c_uint8)), POINTER(c_size_t),
                               POINTER(Timings)]),

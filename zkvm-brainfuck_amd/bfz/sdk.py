@@ -881,6 +881,33 @@ def uni_stark_check(chip: int, trace, on_device: bool = True, per_row: bool = Fa
     return _uni_check_result(out, rows)
 
 
+def _constraint_tables(k: int):
+    """(counts uint64[K], first_rows int64[K], their ctypes pointers)"""
+    import numpy as np
+    counts, first = np.zeros(k, dtype=np.uint64), np.full(k, -1, dtype=np.int64)
+    return (counts, first, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            first.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+
+
+def uni_stark_check_constraints(chip: int, trace, on_device: bool = True):
+    """uni_stark_check without stopping at a row's first failing constraint
+    (bfz_uni_check_constraints): (summary, counts, first_rows).  The summary is uni_stark_check's;
+    counts[k] is the number of rows that violate constraint k and first_rows[k] the smallest of
+    them (-1: none), numpy uint64[K] / int64[K] with the K of uni_stark_info."""
+    import numpy as np
+    if on_device:
+        init()
+    m = np.ascontiguousarray(trace, dtype=np.uint32)
+    if m.ndim != 2:
+        raise ValueError("uni_stark_check_constraints: the trace must be a (height, width) matrix")
+    out = _lib.UniCheckC()
+    counts, first, pc, pf = _constraint_tables(uni_stark_info(chip).num_constraints)
+    check(lib().bfz_uni_check_constraints(
+        int(chip), m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), m.shape[0], m.shape[1],
+        int(bool(on_device)), ctypes.byref(out), pc, pf))
+    return _uni_check_result(out), counts, first
+
+
 def _raise_if_failing(res: UniCheckResult) -> None:
     if res.failing_rows:
         raise BfzError(f"uni_stark_prove: the trace violates the AIR: {res}")
@@ -990,6 +1017,31 @@ def _uni_stark_prove_record(self, pk: BfProvingKey, stdin, chips=UNI_STARK_CHIPS
 
 
 ProverClient.uni_stark_prove_record = _uni_stark_prove_record
+
+
+def _uni_stark_check_constraints_record(self, pk: BfProvingKey, stdin, chip: int):
+    """uni_stark_check_constraints of one chip of (pk's program, stdin) on the trace the device
+    generates (bfz_record_uni_check_constraints): (summary, counts, first_rows), or None when the
+    record does not include the chip."""
+    init(self.device)
+    buf, n = u8buf(bytes(stdin))
+    rec = ctypes.c_void_p()
+    cyc = ctypes.c_uint64()
+    counts, first, pc, pf = _constraint_tables(uni_stark_info(chip).num_constraints)
+    _lib.check(lib().bfz_record_new(ctypes.c_void_p(pk.handle), buf, n, ctypes.byref(rec),
+                                    ctypes.byref(cyc)))
+    try:
+        res = _lib.UniCheckC()
+        rc = lib().bfz_record_uni_check_constraints(rec, int(chip), ctypes.byref(res), pc, pf)
+        if rc == 1:
+            return None
+        _lib.check(rc)
+        return _uni_check_result(res), counts, first
+    finally:
+        lib().bfz_record_free(rec)
+
+
+ProverClient.uni_stark_check_constraints_record = _uni_stark_check_constraints_record
 
 
 # ---- caller-defined AIRs as constraint programs (bfz_air_*): uni_stark_prove / uni_stark_verify
@@ -1168,6 +1220,24 @@ def air_check(prog: bytes, trace, on_device: bool = True, per_row: bool = False)
                               m.shape[0], m.shape[1], int(bool(on_device)), ctypes.byref(out),
                               rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if per_row else None))
     return _uni_check_result(out, rows)
+
+
+def air_check_constraints(prog: bytes, trace, on_device: bool = True):
+    """uni_stark_check_constraints for a constraint program (bfz_air_check_constraints):
+    (summary, counts, first_rows) with the program's K; chip = -1 in the summary."""
+    import numpy as np
+    if on_device:
+        init()
+    m = np.ascontiguousarray(trace, dtype=np.uint32)
+    if m.ndim != 2:
+        raise ValueError("air_check_constraints: the trace must be a (height, width) matrix")
+    out = _lib.UniCheckC()
+    counts, first, pc, pf = _constraint_tables(air_info(prog).num_constraints)
+    buf, n = u8buf(prog)
+    check(lib().bfz_air_check_constraints(
+        buf, n, m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), m.shape[0], m.shape[1],
+        int(bool(on_device)), ctypes.byref(out), pc, pf))
+    return _uni_check_result(out), counts, first
 
 
 def air_prove(prog: bytes, trace, ch: Optional[Challenger] = None, check: bool = False) -> bytes:

@@ -98,5 +98,9 @@ void launch_quotient_prog(int lqd, const uint32_t* code_dev, int ncode, const ui
 // failing rows}; per_row_dev (optional) by storage position.
 void launch_check_prog(const uint32_t* code_dev, int ncode, const uint32_t* mainc, size_t h, int K,
                        unsigned long long* res_dev, int32_t* per_row_dev, hipStream_t st);
+// The constraint profile of the same trace (debug_check.h profile_air_resident): res = the two
+// words above, then count[K] and first[K] as 64-bit words, first starting at ~0.
+void launch_profile_prog(const uint32_t* code_dev, int ncode, const uint32_t* mainc, size_t h, int K,
+                         unsigned long long* res_dev, hipStream_t st);
 
 }  // namespace bfz

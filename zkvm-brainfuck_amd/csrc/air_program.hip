@@ -113,6 +113,31 @@ __global__ __launch_bounds__(256) void k_check_prog(const uint32_t* __restrict__
   reduce_failures(idx, i, K, res);
 }
 
+// k_profile_prog: k_check_prog's frame with the profile's sink (debug_check.h).  The block's
+// count[K] / first[K] tables follow the slot file in LDS: 32 KiB + 4 KiB + reduce_failures' 48
+// bytes = 36912 static, 4 blocks (16 waves) per CU of 160 KiB -- what k_check_prog's 32816 bytes
+// give it, so the tables cost no occupancy.  sink.n advances with the wave-uniform list, so the
+// table index is a scalar.  A thread past the last row interprets row 0 and is ignored: every
+// lane reaches every EMIT, and the slot file is per thread as before.
+__global__ __launch_bounds__(256) void k_profile_prog(const uint32_t* __restrict__ code, int ncode,
+                                                      const uint32_t* __restrict__ mainc,
+                                                      uint32_t n, int logn, int K,
+                                                      unsigned long long* __restrict__ res) {
+  __shared__ uint32_t slots[BFZ_AIR_MAX_LIVE][256];
+  __shared__ uint32_t s_cnt[BFZ_AIR_MAX_CONSTRAINTS], s_fst[BFZ_AIR_MAX_CONSTRAINTS];
+  profile_clear(s_cnt, s_fst, K);
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool has_row = t < n;
+  const uint32_t ts = has_row ? t : 0;  // in bounds whatever t
+  const uint32_t i = dbitrev(ts, logn);
+  const uint32_t tn = dbitrev((i + 1) & (n - 1), logn);  // h = 1: the row is its own next
+  ProfileSink sink{s_cnt, s_fst, has_row ? i : PROFILE_NO_ROW};
+  run_program((ConstWords)code, ncode, slots, mainc, n, ts * 4u, tn * 4u, i == 0 ? ONE : 0u,
+              i == n - 1 ? ONE : 0u, i == n - 1 ? 0u : ONE, sink);
+  profile_flush(s_cnt, s_fst, K, res + 2);
+  reduce_failures(sink.first, i, K, res);
+}
+
 void launch_quotient_prog(int lqd, const uint32_t* code_dev, int ncode, const uint32_t* mainc,
                           int logN, const QuotParams* qp_dev, const uint32_t* twf,
                           const uint32_t* sel_inv, const QuotOut& qo, hipStream_t st) {
@@ -133,9 +158,19 @@ void launch_check_prog(const uint32_t* code_dev, int ncode, const uint32_t* main
   KCHECK();
 }
 
+void launch_profile_prog(const uint32_t* code_dev, int ncode, const uint32_t* mainc, size_t h, int K,
+                         unsigned long long* res_dev, hipStream_t st) {
+  if (K < 1 || K > BFZ_AIR_MAX_CONSTRAINTS)
+    throw std::runtime_error("check: the program's constraint count is outside the profile's table");
+  hipLaunchKernelGGL(k_profile_prog, dim3(ceil_div(h, 256)), dim3(256), 0, st, code_dev, ncode,
+                     mainc, (uint32_t)h, log2i(h), K, res_dev);
+  KCHECK();
+}
+
 // kernels a proof or a check of a program launches (gpu.h PreloadKernels)
 static PreloadKernels preload_air_program{(const void*)&k_quotient_prog<0>,
                                           (const void*)&k_quotient_prog<1>,
-                                          (const void*)&k_check_prog};
+                                          (const void*)&k_check_prog,
+                                          (const void*)&k_profile_prog};
 
 }  // namespace bfz

@@ -1480,6 +1480,71 @@ int bfz_record_uni_check(const bfz_record* rec, int chip, bfz_uni_check_result* 
   });
 }
 
+// ---- the constraint profile: the three row checks with per-constraint counts and first rows
+}  // extern "C"
+namespace {
+// The host-trace half of bfz_uni_check_constraints / bfz_air_check_constraints (the checks are
+// the callers', in the first-fail calls' order).
+void profile_trace(const bfz::UniAir& air, const uint32_t* trace, size_t height, size_t width,
+                   int on_device, bfz_uni_check_result* out, uint64_t* counts, int64_t* first_rows) {
+  bfz::ChipCheck cc;
+  if (!on_device) {
+    for (size_t i = 0; i < height * width; i++)
+      if (trace[i] >= kb::P) bfz::uni_noncanonical_throw(air.name);
+    bfz::profile_air_host(air, trace, height, cc, counts, first_rows);
+  } else {
+    hipStream_t st = bfz::stream();
+    const bfz::DBuf<uint32_t> evals = bfz::uni_upload_trace(width, air.name, trace, height, st);
+    bfz::profile_air_resident(air, evals.p, height, cc, counts, first_rows, st);
+  }
+  to_c(cc, out);
+}
+}  // namespace
+extern "C" {
+
+int bfz_uni_check_constraints(int chip, const uint32_t* trace, size_t height, size_t width,
+                              int on_device, bfz_uni_check_result* out_summary, uint64_t* counts,
+                              int64_t* first_rows) {
+  return guarded([&] {
+    if (!trace || !out_summary || !counts || !first_rows) throw std::runtime_error("null argument");
+    bfz::uni_dims_or_throw(chip, height, width);
+    profile_trace(bfz::uni_air_of_chip(chip), trace, height, width, on_device, out_summary, counts,
+                  first_rows);
+    return 0;
+  });
+}
+
+int bfz_air_check_constraints(const uint8_t* prog, size_t len, const uint32_t* trace, size_t height,
+                              size_t width, int on_device, bfz_uni_check_result* out_summary,
+                              uint64_t* counts, int64_t* first_rows) {
+  return guarded([&] {
+    if (!prog || !trace || !out_summary || !counts || !first_rows)
+      throw std::runtime_error("null argument");
+    const bfz::AirProgram p = bfz::air_compile(prog, len);
+    const bfz::UniAir air = bfz::uni_air_of_program(p);
+    bfz::uni_dims_or_throw(air, height, width);
+    profile_trace(air, trace, height, width, on_device, out_summary, counts, first_rows);
+    return 0;
+  });
+}
+
+int bfz_record_uni_check_constraints(const bfz_record* rec, int chip,
+                                     bfz_uni_check_result* out_summary, uint64_t* counts,
+                                     int64_t* first_rows) {
+  return guarded([&] {
+    if (!rec || !out_summary || !counts || !first_rows) throw std::runtime_error("null argument");
+    const bfz::UniAir air = bfz::uni_air_of_chip(chip);  // throws as uni_air_shape_or_throw
+    bfz::DeviceTraces dt;
+    const int k = record_chip_traces(rec, chip, dt, nullptr);
+    if (k < 0) return 1;
+    bfz::ChipCheck cc;
+    bfz::profile_air_resident(air, dt.evals[k].p, dt.heights[k], cc, counts, first_rows,
+                              bfz::stream());
+    to_c(cc, out_summary);
+    return 0;
+  });
+}
+
 int bfz_record_uni_prove(const bfz_record* rec, int chip, bfz_challenger* ch, uint8_t** proof,
                          size_t* len, bfz_timings* t) {
   return guarded([&] {

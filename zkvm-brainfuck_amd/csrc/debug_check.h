@@ -72,6 +72,35 @@ KB_HD int check_row_air(const uint32_t* L, const uint32_t* N, bool is_first, boo
   return check_row<CHIP, false>(L, N, none, none, nullptr, nullptr, is_first, is_last, z, nullptr, z);
 }
 
+// The AIR-only row into any accumulator: check_row<CHIP, false>'s body with the sink left to the
+// caller (the constraint profile's sinks, which do not stop at the first failure).
+template <int CHIP, class Acc>
+KB_HD void eval_row_air(const uint32_t* L, const uint32_t* N, bool is_first, bool is_last, Acc& acc) {
+  const uint32_t none[1] = {0};
+  const uint32_t first = is_first ? kb::ONE : 0, last = is_last ? kb::ONE : 0,
+                 trans = is_last ? 0 : kb::ONE;
+  Air<BaseOps, Acc> air{L, N, none, none, first, last, trans, acc};
+  air.template eval_air<CHIP>();
+}
+
+// The constraint profile's host sink: every emission that is not zero is counted under its index,
+// and the first row that reaches an index is kept (the caller walks the rows in natural order).
+// n / first are FirstFailAcc's, so the summary is the first-fail check's.
+struct ProfileAcc {
+  uint64_t* counts;
+  int64_t* first_rows;
+  int64_t row;
+  int n = 0, first = -1;
+  KB_HD bool emit(uint32_t c) {
+    if (c != 0) {
+      if (first < 0) first = n;
+      if (counts[n]++ == 0) first_rows[n] = row;
+    }
+    n++;
+    return true;  // (air_run: go on)
+  }
+};
+
 // One row's interactions for the balance table (lookup/debug.rs:79-116): per LookupKind the sum
 // of +-mult / (alpha + kind + sum_v beta^(v+1) val_v) over the chip's lookups whose multiplicity
 // is not zero, the sum of the signed multiplicities (a field element) and their number.  The
@@ -198,6 +227,16 @@ void check_air_host(const UniAir& air, const uint32_t* main, size_t h, ChipCheck
                     int32_t* per_row);
 void check_air_resident(const UniAir& air, const uint32_t* mainc, size_t h, ChipCheck& out,
                         int32_t* per_row, hipStream_t st);
+// The constraint profile of an AIR-only check: besides the summary (the one check_air_host /
+// check_air_resident give for the same trace), counts[k] = the rows on which constraint k is not
+// zero and first_rows[k] = the smallest of them in natural order, -1 if none; K entries each, on
+// the host.  Resident: the kernels k_profile_air<CHIP> / k_profile_prog keep the two tables per
+// block in LDS and flush the entries that are not zero; one copy of 2 + 2K words comes back
+// (syncs st).
+void profile_air_host(const UniAir& air, const uint32_t* main, size_t h, ChipCheck& out,
+                      uint64_t* counts, int64_t* first_rows);
+void profile_air_resident(const UniAir& air, const uint32_t* mainc, size_t h, ChipCheck& out,
+                          uint64_t* counts, int64_t* first_rows, hipStream_t st);
 // chip, height, K and the number of LogUp batches of a result.
 void fill_chip_header(int chip, size_t h, ChipCheck& out);
 // Fills out.{failing_rows, first_row, first_constraint} from the two downloaded words.
@@ -252,6 +291,74 @@ __device__ __forceinline__ void reduce_failures(int idx, uint32_t i, int K,
     if (cnt) {
       atomicMin(&res[0], k);
       atomicAdd(&res[1], (unsigned long long)cnt);
+    }
+  }
+}
+
+// ---- the constraint profile (k_profile_air<CHIP> in debug_check.hip, k_profile_prog in
+// air_program.hip).  The constraint index at an emission is the same in every lane -- the compiled
+// templates are straight-line code and the interpreter's list is wave-uniform -- so a wave settles
+// an emission among its lanes and touches the block's tables once: a ballot of c != 0, and only
+// when some lane fails the popcount into count[k] and the wave's smallest failing row into
+// first[k], both by lane 0 (two LDS atomics per wave and failing constraint, however many lanes
+// fail).  A valid trace pays the ballot and a scalar branch per constraint.
+// Every lane of the wave must reach emit (the minimum is a full-wave butterfly): a thread past the
+// last row runs the row function on row 0 with row = PROFILE_NO_ROW and never fails.
+constexpr uint32_t PROFILE_NO_ROW = ~0u;
+constexpr int PROFILE_CHIP_K = 64;  // k_profile_air's table size; the compiled chips have K <= 44
+
+__device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t o = __shfl_xor(v, off);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+// Device only: emit is KB_HD because Air<>'s members that call it are, and its host body is never
+// run (the host path's sink is ProfileAcc).
+struct ProfileSink {
+  uint32_t* cnt;  // the block's tables (LDS): rows failing constraint k, the smallest of them
+  uint32_t* fst;
+  uint32_t row;   // the thread's natural row, or PROFILE_NO_ROW
+  int n = 0, first = -1;  // as FirstFailSink
+  KB_HD void emit(uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const bool fail = c != 0 && row != PROFILE_NO_ROW;
+    const unsigned long long votes = __ballot(fail);
+    if (votes) {  // wave-uniform
+      if (fail && first < 0) first = n;
+      const uint32_t r = wave_min32(fail ? row : PROFILE_NO_ROW);
+      if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&cnt[n], (uint32_t)__popcll(votes));
+        atomicMin(&fst[n], r);
+      }
+    }
+#endif
+    n++;
+  }
+};
+
+// Block start: count = 0, first = none; ends with the barrier the emissions need.
+__device__ __forceinline__ void profile_clear(uint32_t* cnt, uint32_t* fst, int K) {
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    cnt[k] = 0;
+    fst[k] = PROFILE_NO_ROW;
+  }
+  __syncthreads();
+}
+
+// Block end: the entries that are not zero into prof = {count[K], first[K]} (64-bit words, first
+// starts at ~0) with device atomics; a block without a failure writes nothing.
+__device__ __forceinline__ void profile_flush(const uint32_t* cnt, const uint32_t* fst, int K,
+                                              unsigned long long* __restrict__ prof) {
+  __syncthreads();
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    const uint32_t c = cnt[k];
+    if (c) {
+      atomicAdd(&prof[k], (unsigned long long)c);
+      atomicMin(&prof[K + k], (unsigned long long)fst[k]);
     }
   }
 }

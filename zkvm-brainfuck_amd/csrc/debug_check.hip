@@ -13,7 +13,9 @@
 // k_balance_reduce in a second launch: no modular atomics, deterministic.
 //
 // These kernels are not part of a proof and are NOT in a PreloadKernels list: bfz_init and the
-// first proof of a process do not pay for them.
+// first proof of a process do not pay for them.  That holds for k_profile_air<CHIP> too: like
+// k_check_air<CHIP> it is loaded by its first launch (k_profile_prog is in air_program.hip's list,
+// beside k_check_prog).
 #include "debug_check.h"
 
 #include <algorithm>
@@ -171,6 +173,37 @@ __global__ __launch_bounds__(256) void k_check_air(const uint32_t* __restrict__ 
   reduce_failures(idx, i, K, res);
 }
 
+// k_profile_air<CHIP>: k_check_air's frame with the profile's sink (debug_check.h) -- every
+// constraint of every row is looked at, and the block's count[K] / first[K] tables (LDS) are
+// flushed into prof, which follows the two words of res.  The emissions are unrolled, so a
+// constraint's table address is a constant.  A thread past the last row (a trace shorter than the
+// block) evaluates row 0 and is ignored: every lane reaches every emission.
+template <int CHIP>
+__global__ __launch_bounds__(256) void k_profile_air(const uint32_t* __restrict__ mainc, uint32_t n,
+                                                     int logn, int K,
+                                                     unsigned long long* __restrict__ res) {
+  constexpr int MW = DBG_MAIN_W[CHIP];
+  __shared__ uint32_t s_cnt[PROFILE_CHIP_K], s_fst[PROFILE_CHIP_K];
+  profile_clear(s_cnt, s_fst, K);
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool has_row = t < n;
+  const uint32_t ts = has_row ? t : 0;  // in bounds whatever t
+  const uint32_t i = dbitrev(ts, logn);
+  const uint32_t tn = dbitrev((i + 1) & (n - 1), logn);  // h = 1: the row is its own next
+  const uint32_t vt = ts * 4u, vn = tn * 4u;              // ts, tn < n <= 2^23
+  uint32_t L[MW], Nx[MW];
+#pragma unroll
+  for (int c = 0; c < MW; c++) {
+    const __amdgpu_buffer_rsrc_t r = rsrc_of(mainc + (size_t)c * n);
+    L[c] = ld_b(r, vt, 0);
+    Nx[c] = ld_b(r, vn, 0);
+  }
+  ProfileSink sink{s_cnt, s_fst, has_row ? i : PROFILE_NO_ROW};
+  eval_row_air<CHIP>(L, Nx, i == 0, i == n - 1, sink);
+  profile_flush(s_cnt, s_fst, K, res + 2);
+  reduce_failures(sink.first, i, K, res);
+}
+
 template <int CHIP>
 static void rows_air_host(const uint32_t* main, size_t h, ChipCheck& out, int32_t* per_row) {
   constexpr int MW = DBG_MAIN_W[CHIP];
@@ -283,6 +316,80 @@ void check_air_resident(int chip, const uint32_t* mainc, size_t h, ChipCheck& ou
                         hipStream_t st) {
   check_air_resident(uni_air_of_chip(chip), mainc, h, out, per_row, st);
 }
+
+// ---- the constraint profile
+template <int CHIP>
+static void profile_rows_host(const uint32_t* main, size_t i, size_t nx, bool last, ProfileAcc& acc) {
+  constexpr int MW = DBG_MAIN_W[CHIP];
+  eval_row_air<CHIP>(main + i * MW, main + nx * MW, i == 0, last, acc);
+}
+
+void profile_air_host(const UniAir& air, const uint32_t* main, size_t h, ChipCheck& out,
+                      uint64_t* counts, int64_t* first_rows) {
+  fill_air_header(air, h, out);
+  std::fill(counts, counts + out.num_constraints, (uint64_t)0);
+  std::fill(first_rows, first_rows + out.num_constraints, (int64_t)-1);
+  out.failing_rows = 0;
+  out.first_row = -1;
+  out.first_constraint = -1;
+  for (size_t i = 0; i < h; i++) {
+    const size_t nx = (i + 1) & (h - 1);
+    const bool last = i == h - 1;
+    ProfileAcc acc{counts, first_rows, (int64_t)i};
+    if (air.prog) {
+      const size_t w = (size_t)air.prog->width;
+      air_run<BaseOps>(*air.prog, main + i * w, main + nx * w, i == 0 ? kb::ONE : 0u,
+                       last ? kb::ONE : 0u, last ? 0u : kb::ONE, acc);
+    } else {
+#define BFZ_AIR_CASE(C) \
+  case C: profile_rows_host<C>(main, i, nx, last, acc); break;
+      switch (air.chip) { BFZ_AIR_CHIPS(BFZ_AIR_CASE) }
+#undef BFZ_AIR_CASE
+    }
+    if (acc.first >= 0 && out.failing_rows++ == 0) {
+      out.first_row = (int64_t)i;
+      out.first_constraint = acc.first;
+    }
+  }
+}
+
+void profile_air_resident(const UniAir& air, const uint32_t* mainc, size_t h, ChipCheck& out,
+                          uint64_t* counts, int64_t* first_rows, hipStream_t st) {
+  fill_air_header(air, h, out);
+  const size_t K = (size_t)out.num_constraints;
+  if (!air.prog && K > (size_t)PROFILE_CHIP_K)
+    throw std::runtime_error("check: the chip has more constraints than the profile's table");
+  // {min(row * K + index) or ~0, failing rows, count[K], first[K] or ~0}: one upload, one download
+  std::vector<unsigned long long> res(2 + 2 * K, 0);
+  res[0] = ~0ull;
+  std::fill(res.begin() + 2 + K, res.end(), ~0ull);
+  DBuf<unsigned long long> resd(res.size());
+  DBuf<uint32_t> code_d;
+  HIP_CHECK(hipMemcpyAsync(resd.p, res.data(), res.size() * 8, hipMemcpyHostToDevice, st));
+  if (air.prog) {
+    const std::vector<uint32_t>& code = air.prog->code;
+    code_d.reset(code.size());
+    HIP_CHECK(hipMemcpyAsync(code_d.p, code.data(), code.size() * 4, hipMemcpyHostToDevice, st));
+    launch_profile_prog(code_d.p, (int)code.size(), mainc, h, (int)K, resd.p, st);
+  } else {
+#define BFZ_AIR_CASE(C)                                                                        \
+  case C:                                                                                      \
+    hipLaunchKernelGGL(k_profile_air<C>, dim3(ceil_div(h, 256)), dim3(256), 0, st, mainc,      \
+                       (uint32_t)h, log2i(h), (int)K, resd.p);                                 \
+    break;
+    switch (air.chip) { BFZ_AIR_CHIPS(BFZ_AIR_CASE) }
+#undef BFZ_AIR_CASE
+    KCHECK();
+  }
+  HIP_CHECK(hipMemcpyAsync(res.data(), resd.p, res.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  decode_check_result(res.data(), out);
+  for (size_t k = 0; k < K; k++) {
+    counts[k] = res[2 + k];
+    first_rows[k] = res[2 + K + k] == ~0ull ? -1 : (int64_t)res[2 + K + k];
+  }
+}
+
 #undef BFZ_AIR_CHIPS
 
 // ------------------------------------------------------------------------ host path
