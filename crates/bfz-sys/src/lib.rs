@@ -284,6 +284,25 @@ pub struct bfz_air_shape {
     pub _pad: i32,
 }
 
+/// The shape of an interaction program and the size of its compiled list (`bfz_lookups_info`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bfz_lookups_shape {
+    pub main_width: i32,
+    pub prep_width: i32,
+    pub n_interactions: i32,
+    pub sends: i32,
+    pub receives: i32,
+    pub perm_width: i32,
+    pub list_words: i32,
+    pub _pad: i32,
+}
+
+/// Limits of a BFL1 interaction program.
+pub const BFZ_LOOKUPS_MAX: usize = 32;
+pub const BFZ_LOOKUPS_MAX_VALUES: usize = 7;
+pub const BFZ_LOOKUPS_MAX_TERMS: usize = 8;
+
 /// Chip word of a BFU1 proof made from a constraint program (`bfz_air_prove`).
 pub const BFZ_AIR_CHIP: u32 = 0xffff_ffff;
 
@@ -468,6 +487,25 @@ extern "C" {
                          proof_len: *mut usize, timings: *mut bfz_timings) -> c_int;
     pub fn bfz_air_verify(prog: *const u8, len: usize, ch: *mut bfz_challenger, proof: *const u8,
                           proof_len: usize, out: *mut bfz_verify_outcome) -> c_int;
+
+    /// LogUp of caller-defined chips as BFL1 interaction programs: `generate_permutation_trace`
+    /// runs over whatever interactions it is handed (crates/stark/src/permutation.rs:75-148), and
+    /// the verifier sums the chips' cumulative sums (crates/stark/src/verifier.rs:210-213).
+    pub fn bfz_lookups_export(chip: c_int, prog: *mut *mut u8, len: *mut usize) -> c_int;
+    pub fn bfz_lookups_info(prog: *const u8, len: usize, out: *mut bfz_lookups_shape) -> c_int;
+    pub fn bfz_lookups_perm_trace(prog: *const u8, len: usize, main: *const u32, prep: *const u32,
+                                  height: usize, alpha: *const u32, beta: *const u32,
+                                  on_device: c_int, out: *mut *mut u32, width: *mut usize,
+                                  cumsum: *mut u32) -> c_int;
+    pub fn bfz_lookups_balance(progs: *const *const u8, lens: *const usize,
+                               mains: *const *const u32, preps: *const *const u32,
+                               heights: *const usize, n_chips: usize, alpha: *const u32,
+                               beta: *const u32, on_device: c_int, cumsums: *mut u32,
+                               total: *mut u32, balanced: *mut c_int) -> c_int;
+
+    pub fn bfz_lookups_time(prog: *const u8, len: usize, chip: c_int, main: *const u32,
+                            prep: *const u32, height: usize, alpha: *const u32, beta: *const u32,
+                            runs: c_int, prog_ms: *mut f32, chip_ms: *mut f32) -> c_int;
 
     pub fn bfz_set_num_queries(num_queries: c_int) -> c_int;
     pub fn bfz_set_pcs_variant(observe_openings: c_int) -> c_int;

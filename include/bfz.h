@@ -743,6 +743,71 @@ int bfz_air_prove(const uint8_t* prog, size_t len, const uint32_t* trace, size_t
 int bfz_air_verify(const uint8_t* prog, size_t len, bfz_challenger* ch, const uint8_t* proof,
                    size_t proof_len, bfz_verify_outcome* out);
 
+/* ---- LogUp for caller-defined chips: interactions as data.  The reference derives the sends and
+ * receives of any AIR (Chip::new, crates/stark/src/chip.rs:65-90), runs
+ * generate_permutation_trace over whatever interactions it is handed
+ * (crates/stark/src/permutation.rs:75-148), and its verifier's last condition is that the chips'
+ * cumulative sums add to zero (crates/stark/src/verifier.rs:210-213).  Here a chip's interactions
+ * arrive as an interaction program, so the permutation trace of a new chip, or of a built-in chip
+ * with one lookup changed, and the balance of a set of chips are computed without rebuilding the
+ * library.
+ *
+ * The program format "BFL1": little-endian u32 words, field values as Montgomery words < p.
+ *     "BFL1" | main_width | prep_width | n_interactions
+ *     per interaction, in chain order (the sends in emission order, then the receives):
+ *         kind | send (1) / receive (0) | n_values | mult : VCOL | n_values x VCOL
+ *     VCOL := constant | n_terms | n_terms x (source 0 = main / 1 = prep, column, weight)
+ * kind is the canonical argument index (LookupKind as usize, crates/stark/src/lookup/lookup.rs:17-42),
+ * below p; a VCOL is a VirtualPairCol, constant + sum weight x column, and one of 0 terms is a
+ * constant.  n_values = 0 is legal: the denominator is then alpha + kind.  Every call validates
+ * the program first (a malformed one: negative status, the message names the word offset; nothing
+ * outside [prog, prog + len) is read; trailing words are an error).
+ *
+ *   bfz_lookups_export      host only: the program of a built-in chip (all eight; Program and Byte
+ *                           use their preprocessed columns); *prog is freed with bfz_free.
+ *   bfz_lookups_info        host only: validates, and reports the widths, the interaction counts,
+ *                           the permutation width in EF columns (ceil(n / 2) + 1,
+ *                           permutation.rs:15-21) and the compiled list's size in words.
+ *   bfz_lookups_perm_trace  bfz_perm_trace's contract: main (and prep; NULL when prep_width is 0)
+ *                           row-major Montgomery words, height a power of two in [1, 2^23], words
+ *                           >= p refused with the bfz_uni_* calls' message; *out (bfz_free) is
+ *                           height x 4 * perm_width row-major in natural row order, *width = 4 *
+ *                           perm_width.  on_device = 0 is a single-threaded host loop (no device
+ *                           needed).  For a built-in chip's exported program the words equal
+ *                           bfz_perm_trace's.  As there, a zero denominator is not detected.
+ *   bfz_lookups_balance     the verifier's sum of cumulative sums == 0 for n_chips caller-defined
+ *                           chips under the caller's challenges: each chip's trace is uploaded and
+ *                           reduced to its cumulative sum on the device; 4 * n_chips + 4 words
+ *                           come back, never a permutation trace.  preps may be NULL when no chip
+ *                           has preprocessed columns.  Returns 0 whenever the check RAN;
+ *                           *balanced = 1 iff total is zero. */
+#define BFZ_LOOKUPS_MAX 32          /* interactions per program: Cpu has 16 */
+#define BFZ_LOOKUPS_MAX_VALUES 7    /* the challenges hold beta^0 .. beta^7 */
+#define BFZ_LOOKUPS_MAX_TERMS 8     /* per VCOL: a Word is 4 */
+typedef struct {
+  int32_t main_width, prep_width, n_interactions, sends, receives;
+  int32_t perm_width, list_words, _pad;   /* EF columns; words of the compiled list */
+} bfz_lookups_shape;
+int bfz_lookups_export(int chip, uint8_t** prog, size_t* len);
+int bfz_lookups_info(const uint8_t* prog, size_t len, bfz_lookups_shape* out);
+int bfz_lookups_perm_trace(const uint8_t* prog, size_t len, const uint32_t* main,
+                           const uint32_t* prep, size_t height, const uint32_t alpha[4],
+                           const uint32_t beta[4], int on_device, uint32_t** out, size_t* width,
+                           uint32_t cumsum[4]);
+int bfz_lookups_balance(const uint8_t* const* progs, const size_t* lens,
+                        const uint32_t* const* mains, const uint32_t* const* preps,
+                        const size_t* heights, size_t n_chips, const uint32_t alpha[4],
+                        const uint32_t beta[4], int on_device, uint32_t* cumsums,
+                        uint32_t total[4], int* balanced);
+
+/* Diagnostic (scripts/lookups_time.py): HIP-event times, in ms, of single launches of the row
+ * kernels alone on one uploaded trace, alternating after one warm-up launch of each:
+ * k_perm_rows_prog<1> on prog -> prog_ms[runs] and, with chip >= 0 (prog must have that chip's
+ * shape), k_perm_rows<chip> -> chip_ms[runs].  Nothing of the traces they write comes back. */
+int bfz_lookups_time(const uint8_t* prog, size_t len, int chip, const uint32_t* main,
+                     const uint32_t* prep, size_t height, const uint32_t alpha[4],
+                     const uint32_t beta[4], int runs, float* prog_ms, float* chip_ms);
+
 /* FRI_QUERIES (kb31_poseidon2.rs:59-62): 1..4096, or 0 = environment FRI_QUERIES / 84. */
 int bfz_set_num_queries(int num_queries);
 

@@ -104,6 +104,13 @@ class AirShapeC(ctypes.Structure):
                 ("live_values", c_int32), ("_pad", c_int32)]
 
 
+class LookupsShapeC(ctypes.Structure):
+    """bfz_lookups_shape: the shape of an interaction program and the size of its compiled list."""
+    _fields_ = [("main_width", c_int32), ("prep_width", c_int32), ("n_interactions", c_int32),
+                ("sends", c_int32), ("receives", c_int32), ("perm_width", c_int32),
+                ("list_words", c_int32), ("_pad", c_int32)]
+
+
 class VerifyOutcomeC(ctypes.Structure):
     """bfz_verify_outcome: one proof's verdict from bfz_verify_batch."""
     _fields_ = [("ok", c_int32), ("query", c_int32), ("why", ctypes.c_char * 120)]
@@ -241,6 +248,20 @@ SIGNATURES = [
                               POINTER(Timings)]),
     ("bfz_air_verify", c_int, [POINTER(c_uint8), c_size_t, POINTER(Challenger), POINTER(c_uint8),
                                c_size_t, POINTER(VerifyOutcomeC)]),
+    ("bfz_lookups_export", c_int, [c_int, POINTER(POINTER(c_uint8)), POINTER(c_size_t)]),
+    ("bfz_lookups_info", c_int, [POINTER(c_uint8), c_size_t, POINTER(LookupsShapeC)]),
+    ("bfz_lookups_perm_trace", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint32),
+                                       POINTER(c_uint32), c_size_t, POINTER(c_uint32),
+                                       POINTER(c_uint32), c_int, POINTER(POINTER(c_uint32)),
+                                       POINTER(c_size_t), POINTER(c_uint32)]),
+    ("bfz_lookups_balance", c_int, [POINTER(POINTER(c_uint8)), POINTER(c_size_t),
+                                    POINTER(POINTER(c_uint32)), POINTER(POINTER(c_uint32)),
+                                    POINTER(c_size_t), c_size_t, POINTER(c_uint32),
+                                    POINTER(c_uint32), c_int, POINTER(c_uint32), POINTER(c_uint32),
+                                    POINTER(c_int)]),
+    ("bfz_lookups_time", c_int, [POINTER(c_uint8), c_size_t, c_int, POINTER(c_uint32),
+                                 POINTER(c_uint32), c_size_t, POINTER(c_uint32), POINTER(c_uint32),
+                                 c_int, POINTER(ctypes.c_float), POINTER(ctypes.c_float)]),
     ("bfz_set_num_queries", c_int, [c_int]),
     ("bfz_set_pcs_variant", c_int, [c_int]),
     ("bfz_set_fault_injection", c_int, [c_int]),

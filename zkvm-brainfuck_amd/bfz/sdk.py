@@ -1278,6 +1278,213 @@ def air_verify(prog: bytes, proof: bytes, ch: Optional[Challenger] = None) -> No
         raise BfzError("uni-STARK verification failed: " + out.why.decode())
 
 
+# ---- LogUp of caller-defined chips as interaction programs (bfz_lookups_*): Chip::new derives the
+# interactions of any AIR (crates/stark/src/chip.rs:65-90) and generate_permutation_trace runs
+# over whatever it is handed (crates/stark/src/permutation.rs:75-148)
+_LOOKUPS_MAGIC = 0x314C4642  # "BFL1"
+LOOKUPS_MAX, LOOKUPS_MAX_VALUES, LOOKUPS_MAX_TERMS = 32, 7, 8
+
+
+def _mont(v: int) -> int:
+    return ((int(v) % _KB_P) << 32) % _KB_P
+
+
+class LookupExpr:
+    """An affine expression over a row, constant + sum weight * column (a VirtualPairCol):
+    + and - with expressions and ints, * with ints.  Canonical integers throughout."""
+    __slots__ = ("const", "terms")
+
+    def __init__(self, const=0, terms=None):
+        self.const, self.terms = int(const) % _KB_P, dict(terms or {})  # {(source, column): weight}
+
+    @staticmethod
+    def _lift(v) -> "LookupExpr":
+        return v if isinstance(v, LookupExpr) else LookupExpr(v)
+
+    def __add__(self, o):
+        o = self._lift(o)
+        terms = dict(self.terms)
+        for k, w in o.terms.items():
+            terms[k] = (terms.get(k, 0) + w) % _KB_P
+        return LookupExpr(self.const + o.const, terms)
+
+    __radd__ = __add__
+
+    def __mul__(self, k):
+        k = int(k)  # (an expression times an expression is not affine)
+        return LookupExpr(self.const * k, {c: w * k % _KB_P for c, w in self.terms.items()})
+
+    __rmul__ = __mul__
+
+    def __neg__(self):
+        return self * -1
+
+    def __sub__(self, o):
+        return self + -self._lift(o)
+
+    def __rsub__(self, o):
+        return self._lift(o) + -self
+
+    def _words(self) -> list:
+        terms = [(k, w) for k, w in self.terms.items() if w]
+        if len(terms) > LOOKUPS_MAX_TERMS:
+            raise ValueError(f"LookupBuilder: more than {LOOKUPS_MAX_TERMS} terms in one expression")
+        out = [_mont(self.const), len(terms)]
+        for (src, col), w in terms:
+            out += [src, col, _mont(w)]
+        return out
+
+
+class LookupBuilder:
+    """Builds a BFL1 interaction program (include/bfz.h) the way an Air::eval calls the lookup
+    builder: main(c) / prep(c) are the row's columns, send / receive take the canonical argument
+    index, the values and the multiplicity as affine expressions (or ints).  program() returns the
+    bytes bfz_lookups_* take: the sends in emission order, then the receives."""
+
+    def __init__(self, main_width: int, prep_width: int = 0):
+        self.main_width, self.prep_width = int(main_width), int(prep_width)
+        self._sends: List[list] = []
+        self._receives: List[list] = []
+
+    def _col(self, src: int, c: int, width: int) -> LookupExpr:
+        c = int(c)
+        if not 0 <= c < width:
+            raise ValueError(f"LookupBuilder: column {c} outside the width {width}")
+        return LookupExpr(0, {(src, c): 1})
+
+    def main(self, c: int) -> LookupExpr:
+        return self._col(0, c, self.main_width)
+
+    def prep(self, c: int) -> LookupExpr:
+        return self._col(1, c, self.prep_width)
+
+    def _interaction(self, send: int, kind: int, values, mult) -> list:
+        values = list(values)
+        if len(values) > LOOKUPS_MAX_VALUES:
+            raise ValueError(f"LookupBuilder: more than {LOOKUPS_MAX_VALUES} values")
+        words = [int(kind), send, len(values)]
+        for e in [mult] + values:
+            words += LookupExpr._lift(e)._words()
+        return words
+
+    def send(self, kind: int, values, mult) -> None:
+        self._sends.append(self._interaction(1, kind, values, mult))
+
+    def receive(self, kind: int, values, mult) -> None:
+        self._receives.append(self._interaction(0, kind, values, mult))
+
+    def program(self) -> bytes:
+        import struct
+        chain = self._sends + self._receives
+        words = [_LOOKUPS_MAGIC, self.main_width, self.prep_width, len(chain)]
+        for it in chain:
+            words += it
+        return struct.pack(f"<{len(words)}I", *words)
+
+
+@dataclass
+class LookupsInfo:
+    """bfz_lookups_shape: perm_width in EF columns, list_words of the compiled list."""
+    main_width: int
+    prep_width: int
+    n_interactions: int
+    sends: int
+    receives: int
+    perm_width: int
+    list_words: int
+
+
+@dataclass
+class LookupsBalance:
+    """bfz_lookups_balance: balanced iff total (the sum of the chips' cumulative sums) is zero."""
+    balanced: bool
+    total: List[int]
+    cumsums: List[List[int]]
+
+
+def lookups_export(chip: int) -> bytes:
+    """bfz_lookups_export (host only): the BFL1 program of a built-in chip's interactions."""
+    ptr = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    check(lib().bfz_lookups_export(int(chip), ctypes.byref(ptr), ctypes.byref(n)))
+    return take_bytes(ptr, n.value)
+
+
+def lookups_info(prog: bytes) -> LookupsInfo:
+    """bfz_lookups_info (host only): validates the program; raises BfzError naming the word
+    offset."""
+    buf, n = u8buf(prog)
+    out = _lib.LookupsShapeC()
+    check(lib().bfz_lookups_info(buf, n, ctypes.byref(out)))
+    return LookupsInfo(out.main_width, out.prep_width, out.n_interactions, out.sends, out.receives,
+                       out.perm_width, out.list_words)
+
+
+def _lookups_trace(m, what):
+    import numpy as np
+    if m is None:
+        return None
+    m = np.ascontiguousarray(m, dtype=np.uint32)
+    if m.ndim != 2:
+        raise ValueError(f"{what}: a trace must be a (height, width) matrix")
+    return m
+
+
+def _lookups_chip_args(info: LookupsInfo, main, prep, what):
+    main, prep = _lookups_trace(main, what), _lookups_trace(prep, what)
+    if main is None or main.shape[1] != info.main_width:
+        raise ValueError(f"{what}: the main trace must have {info.main_width} columns")
+    if info.prep_width and (prep is None or prep.shape != (main.shape[0], info.prep_width)):
+        raise ValueError(f"{what}: the prep trace must be ({main.shape[0]}, {info.prep_width})")
+    return main, prep if info.prep_width else None
+
+
+def lookups_perm_trace(prog: bytes, main, prep, alpha, beta, on_device: bool = True):
+    """bfz_lookups_perm_trace: generate_permutation_trace for an interaction program.  main / prep
+    (None without preprocessed columns): (height, width) Montgomery words; alpha, beta: 4
+    Montgomery words each.  Returns (perm, cumsum): the (height, 4 * perm_width) flattened
+    permutation trace in natural row order and the 4 words of the cumulative sum.  A zero
+    denominator is not detected."""
+    import numpy as np
+    if on_device:
+        init()
+    main, prep = _lookups_chip_args(lookups_info(prog), main, prep, "lookups_perm_trace")
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    out, w, cs = u32p(), ctypes.c_size_t(), (ctypes.c_uint32 * 4)()
+    buf, n = u8buf(prog)
+    check(lib().bfz_lookups_perm_trace(
+        buf, n, main.ctypes.data_as(u32p), prep.ctypes.data_as(u32p) if prep is not None else None,
+        main.shape[0], (ctypes.c_uint32 * 4)(*alpha), (ctypes.c_uint32 * 4)(*beta),
+        int(bool(on_device)), ctypes.byref(out), ctypes.byref(w), cs))
+    perm = np.ctypeslib.as_array(out, shape=(main.shape[0], w.value)).copy()
+    lib().bfz_free(out)
+    return perm, list(cs)
+
+
+def lookups_balance(progs, mains, preps, alpha, beta, on_device: bool = True) -> LookupsBalance:
+    """bfz_lookups_balance: the verifier's sum of cumulative sums == 0
+    (crates/stark/src/verifier.rs:210-213) for caller-defined chips under the caller's challenges.
+    progs, mains, preps: one entry per chip (a prep entry is None without preprocessed columns)."""
+    if on_device:
+        init()
+    k = len(progs)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    chips = [_lookups_chip_args(lookups_info(p), m, pr, "lookups_balance")
+             for p, m, pr in zip(progs, mains, preps)]
+    bufs = [u8buf(p) for p in progs]
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    cprogs = (u8p * k)(*[ctypes.cast(b, u8p) for b, _ in bufs])
+    clens = (ctypes.c_size_t * k)(*[n for _, n in bufs])
+    cmains = (u32p * k)(*[m.ctypes.data_as(u32p) for m, _ in chips])
+    cpreps = (u32p * k)(*[pr.ctypes.data_as(u32p) if pr is not None else u32p() for _, pr in chips])
+    cheights = (ctypes.c_size_t * k)(*[m.shape[0] for m, _ in chips])
+    cums, total, ok = (ctypes.c_uint32 * (4 * k))(), (ctypes.c_uint32 * 4)(), ctypes.c_int()
+    check(lib().bfz_lookups_balance(cprogs, clens, cmains, cpreps, cheights, k,
+                                    (ctypes.c_uint32 * 4)(*alpha), (ctypes.c_uint32 * 4)(*beta),
+                                    int(bool(on_device)), cums, total, ctypes.byref(ok)))
+    return LookupsBalance(bool(ok.value), list(total), [list(cums[4 * i:4 * i + 4]) for i in range(k)])
+
+
 def set_num_queries(q: int) -> None:
     """FRI_QUERIES override (crates/stark/src/kb31_poseidon2.rs:59-62); 0 = environment/84."""
     check(lib().bfz_set_num_queries(int(q)))

@@ -19,6 +19,7 @@
 #include "fri.h"
 #include "logup.h"
 #include "lookup_debug.h"
+#include "lookup_program.h"
 #include "merkle.h"
 #include "ntt.h"
 #include "pcs_sharded.h"
@@ -1462,6 +1463,201 @@ int bfz_air_verify(const uint8_t* prog, size_t len, bfz_challenger* ch, const ui
     uni_opts(uo);
     to_c(bfz::uni_verify(bfz::uni_air_of_program(p), c, proof, proof_len, uo), out);
     to_c(c, ch);
+    return 0;
+  });
+}
+
+// ---- LogUp of caller-defined chips as interaction programs (lookup_program.h)
+}  // extern "C"
+namespace {
+bfz::PermChallenges lookup_challenges(const uint32_t alpha[4], const uint32_t beta[4]) {
+  bfz::PermChallenges ch;
+  ch.alpha = ef_arg(alpha, "challenge");
+  const kb::EF b = ef_arg(beta, "challenge");
+  ch.beta_pows[0] = kb::ef_one();
+  for (int j = 1; j < 8; j++) ch.beta_pows[j] = kb::ef_mul(ch.beta_pows[j - 1], b);
+  return ch;
+}
+void lookup_dims_or_throw(const bfz::LookupProgram& p, const uint32_t* main, const uint32_t* prep,
+                          size_t h) {
+  if (!main) throw std::runtime_error("null argument");
+  if (p.prep_w && !prep) throw std::runtime_error("lookups: the program has preprocessed columns");
+  if (h == 0 || (h & (h - 1)) || h > ((size_t)1 << 23))
+    throw std::runtime_error("lookups: height not a power of two in [1, 2^23]");
+}
+// The host path's word check (mmul needs words < p); the device path checks after the upload.
+void lookup_canonical_or_throw(const bfz::LookupProgram& p, const uint32_t* main,
+                               const uint32_t* prep, size_t h) {
+  for (size_t i = 0; i < h * (size_t)p.main_w; i++)
+    if (main[i] >= kb::P) bfz::uni_noncanonical_throw("lookups");
+  for (size_t i = 0; i < h * (size_t)p.prep_w; i++)
+    if (prep[i] >= kb::P) bfz::uni_noncanonical_throw("lookups");
+}
+// One chip on the device: its traces and list uploaded, its cumulative sum in *cs_dev and, with
+// perm_dev, its permutation trace (column-major, bit-reversed rows).
+void lookup_chip_device(const bfz::LookupProgram& p, const uint32_t* main, const uint32_t* prep,
+                        size_t h, const bfz::PermChallenges* ch_dev, uint32_t* perm_dev,
+                        kb::EF* cs_dev, hipStream_t st) {
+  const bfz::DBuf<uint32_t> mc = bfz::uni_upload_trace((size_t)p.main_w, "lookups", main, h, st);
+  bfz::DBuf<uint32_t> pc;
+  if (p.prep_w) pc = bfz::uni_upload_trace((size_t)p.prep_w, "lookups", prep, h, st);
+  bfz::DBuf<uint32_t> list(p.list.size());
+  bfz::upload_async(list.p, p.list.data(), p.list.size() * 4, st);
+  bfz::perm_trace_prog(p, list.p, mc.p, p.prep_w ? pc.p : nullptr, h, ch_dev, perm_dev, cs_dev, st);
+}
+}  // namespace
+extern "C" {
+
+int bfz_lookups_export(int chip, uint8_t** prog, size_t* len) {
+  return guarded([&] {
+    if (!prog || !len) throw std::runtime_error("null argument");
+    return emit(bfz::lookups_export(chip), prog, len);
+  });
+}
+
+int bfz_lookups_info(const uint8_t* prog, size_t len, bfz_lookups_shape* out) {
+  return guarded([&] {
+    if (!prog || !out) throw std::runtime_error("null argument");
+    const bfz::LookupProgram p = bfz::lookups_compile(prog, len);
+    static_assert(sizeof(bfz_lookups_shape) == 32, "bfz_lookups_shape has no gaps");
+    std::memset(out, 0, sizeof *out);
+    out->main_width = p.main_w;
+    out->prep_width = p.prep_w;
+    out->n_interactions = p.n;
+    out->sends = p.sends;
+    out->receives = p.receives;
+    out->perm_width = p.perm_width();
+    out->list_words = (int32_t)p.list.size();
+    return 0;
+  });
+}
+
+// A zero denominator is not detected, on either path (as in bfz_perm_trace): its inverse is taken
+// as 0.
+int bfz_lookups_perm_trace(const uint8_t* prog, size_t len, const uint32_t* main,
+                           const uint32_t* prep, size_t n, const uint32_t alpha[4],
+                           const uint32_t beta[4], int on_device, uint32_t** out, size_t* width,
+                           uint32_t cumsum[4]) {
+  return guarded([&] {
+    if (!prog || !alpha || !beta || !out || !width || !cumsum) throw std::runtime_error("null argument");
+    const bfz::LookupProgram p = bfz::lookups_compile(prog, len);
+    lookup_dims_or_throw(p, main, prep, n);
+    const bfz::PermChallenges ch = lookup_challenges(alpha, beta);
+    const size_t w = 4 * (size_t)p.perm_width();
+    std::unique_ptr<uint32_t, decltype(&std::free)> o((uint32_t*)std::malloc(n * w * 4 + 4), &std::free);
+    if (!o) throw std::runtime_error("out of host memory");
+    kb::EF cs;
+    if (!on_device) {
+      lookup_canonical_or_throw(p, main, prep, n);
+      bfz::lookups_perm_trace_host(p, main, prep, n, ch, o.get(), &cs);
+    } else {
+      hipStream_t st = bfz::stream();
+      bfz::DBuf<uint32_t> pe(n * w);
+      bfz::DBuf<kb::EF> csd(1);
+      bfz::DBuf<bfz::PermChallenges> chd(1);
+      bfz::upload_async(chd.p, &ch, sizeof(ch), st);
+      lookup_chip_device(p, main, prep, n, chd.p, pe.p, csd.p, st);
+      std::vector<uint32_t> cm(n * w);
+      HIP_CHECK(hipMemcpyAsync(cm.data(), pe.p, cm.size() * 4, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(&cs, csd.p, 16, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+      const int logh = bfz::log2i(n);
+      for (size_t r = 0; r < n; r++)  // column-major bit-reversed -> row-major natural
+        for (size_t c = 0; c < w; c++) o.get()[r * w + c] = cm[c * n + bfz::bitrev32((uint32_t)r, logh)];
+    }
+    std::memcpy(cumsum, cs.c, 16);
+    *out = o.release();
+    *width = w;
+    return 0;
+  });
+}
+
+int bfz_lookups_balance(const uint8_t* const* progs, const size_t* lens,
+                        const uint32_t* const* mains, const uint32_t* const* preps,
+                        const size_t* heights, size_t n_chips, const uint32_t alpha[4],
+                        const uint32_t beta[4], int on_device, uint32_t* cumsums,
+                        uint32_t total[4], int* balanced) {
+  return guarded([&] {
+    if (!progs || !lens || !mains || !heights || !alpha || !beta || !cumsums || !total || !balanced)
+      throw std::runtime_error("null argument");
+    if (n_chips < 1 || n_chips > 65536) throw std::runtime_error("lookups: chip count not in [1, 65536]");
+    const bfz::PermChallenges ch = lookup_challenges(alpha, beta);
+    std::vector<bfz::LookupProgram> ps;  // every program and shape is checked before any work
+    for (size_t i = 0; i < n_chips; i++) {
+      if (!progs[i]) throw std::runtime_error("null argument");
+      ps.push_back(bfz::lookups_compile(progs[i], lens[i]));
+      lookup_dims_or_throw(ps[i], mains[i], preps ? preps[i] : nullptr, heights[i]);
+    }
+    std::vector<kb::EF> cs(n_chips + 1, kb::ef_zero());  // the chips' sums, then the total
+    if (!on_device) {
+      for (size_t i = 0; i < n_chips; i++) {
+        const uint32_t* prep = preps ? preps[i] : nullptr;
+        lookup_canonical_or_throw(ps[i], mains[i], prep, heights[i]);
+        bfz::lookups_perm_trace_host(ps[i], mains[i], prep, heights[i], ch, nullptr, &cs[i]);
+        cs[n_chips] = kb::ef_add(cs[n_chips], cs[i]);
+      }
+    } else {
+      hipStream_t st = bfz::stream();
+      bfz::DBuf<kb::EF> csd(n_chips + 1);
+      bfz::DBuf<bfz::PermChallenges> chd(1);
+      bfz::upload_async(chd.p, &ch, sizeof(ch), st);
+      for (size_t i = 0; i < n_chips; i++)
+        lookup_chip_device(ps[i], mains[i], preps ? preps[i] : nullptr, heights[i], chd.p, nullptr,
+                           csd.p + i, st);
+      bfz::ef_total(csd.p, n_chips, csd.p + n_chips, st);
+      HIP_CHECK(hipMemcpyAsync(cs.data(), csd.p, cs.size() * sizeof(kb::EF), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    }
+    std::memcpy(cumsums, cs.data(), n_chips * sizeof(kb::EF));
+    std::memcpy(total, cs[n_chips].c, 16);
+    *balanced = kb::ef_is_zero(cs[n_chips]) ? 1 : 0;
+    return 0;
+  });
+}
+
+int bfz_lookups_time(const uint8_t* prog, size_t len, int chip, const uint32_t* main,
+                     const uint32_t* prep, size_t n, const uint32_t alpha[4], const uint32_t beta[4],
+                     int runs, float* prog_ms, float* chip_ms) {
+  return guarded([&] {
+    if (!prog || !alpha || !beta || !prog_ms || (chip >= 0 && !chip_ms)) throw std::runtime_error("null argument");
+    if (chip >= bfz::NUM_CHIPS || runs < 1) throw std::runtime_error("lookups_time: bad chip or run count");
+    const bfz::LookupProgram p = bfz::lookups_compile(prog, len);
+    lookup_dims_or_throw(p, main, prep, n);
+    if (chip >= 0 && (p.main_w != bfz::CHIP_INFO[chip].main_w || p.prep_w != bfz::CHIP_INFO[chip].prep_w ||
+                      p.n != bfz::CHIP_INFO[chip].n_interactions))
+      throw std::runtime_error("lookups_time: the program does not have the chip's shape");
+    const bfz::PermChallenges ch = lookup_challenges(alpha, beta);
+    hipStream_t st = bfz::stream();
+    const bfz::DBuf<uint32_t> mc = bfz::uni_upload_trace((size_t)p.main_w, "lookups", main, n, st);
+    bfz::DBuf<uint32_t> pc;
+    if (p.prep_w) pc = bfz::uni_upload_trace((size_t)p.prep_w, "lookups", prep, n, st);
+    bfz::DBuf<uint32_t> list(p.list.size()), pe(n * 4 * (size_t)p.perm_width());
+    bfz::DBuf<kb::EF> rows(n);
+    bfz::DBuf<bfz::PermChallenges> chd(1);
+    bfz::upload_async(list.p, p.list.data(), p.list.size() * 4, st);
+    bfz::upload_async(chd.p, &ch, sizeof(ch), st);
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    auto timed = [&](bool compiled) {
+      HIP_CHECK(hipEventRecord(e0, st));
+      if (compiled) bfz::perm_rows(chip, mc.p, pc.p, n, chd.p, pe.p, rows.p, st);
+      else bfz::perm_rows_prog(p, list.p, mc.p, pc.p, n, chd.p, pe.p, rows.p, st);
+      HIP_CHECK(hipEventRecord(e1, st));
+      HIP_CHECK(hipEventSynchronize(e1));
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      return ms;
+    };
+    for (int r = -1; r < runs; r++) {  // r = -1: the warm-up launches
+      const float a = timed(false), b = chip >= 0 ? timed(true) : 0.f;
+      if (r >= 0) {
+        prog_ms[r] = a;
+        if (chip >= 0) chip_ms[r] = b;
+      }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
     return 0;
   });
 }

@@ -17,6 +17,15 @@ struct PermChallenges {
 // ch: DEVICE memory (the prover samples the challenges on the device, challenge_perm).
 void perm_trace(int chip, const uint32_t* mainc, const uint32_t* prepc, size_t n,
                 const PermChallenges* ch, uint32_t* perm, kb::EF* cumsum_dev, hipStream_t st);
+// The first half of perm_trace alone (k_perm_rows<chip>): the batch columns of perm and
+// rowsum[t] = the sum of row t's batch values (bit-reversed storage).
+void perm_rows(int chip, const uint32_t* mainc, const uint32_t* prepc, size_t n,
+               const PermChallenges* ch, uint32_t* perm, kb::EF* rowsum, hipStream_t st);
+// The second half of perm_trace, for any row kernel: rows[t] = the sum of row t's batch values
+// (bit-reversed storage).  Writes their natural-order running sum as the EF column at base
+// column col0 of perm and the cumulative sum; with perm == nullptr the cumulative sum alone.
+void perm_running_sum(const kb::EF* rows, size_t n, uint32_t* perm, int col0, kb::EF* cumsum_dev,
+                      hipStream_t st);
 // Device transcript step after the main commit: the DuplexChallenger state `ch` (device
 // memory, updated in place) observes the 8-word root and samples the LogUp alpha and beta
 // (prover.rs:269-272); out receives alpha and beta^0..7.  The host replays the same step when

@@ -299,29 +299,41 @@ static void launch_rows(const uint32_t* mainc, const uint32_t* prepc, size_t n,
 
 void perm_trace(int chip, const uint32_t* mainc, const uint32_t* prepc, size_t n,
                 const PermChallenges* ch, uint32_t* perm, EF* cumsum_dev, hipStream_t st) {
-  const int logn = log2i(n);
   DBuf<EF> rows(n);
+  perm_rows(chip, mainc, prepc, n, ch, perm, rows.p, st);
+  perm_running_sum(rows.p, n, perm, 4 * (perm_width(chip) - 1), cumsum_dev, st);
+}
+
+void perm_rows(int chip, const uint32_t* mainc, const uint32_t* prepc, size_t n,
+               const PermChallenges* ch, uint32_t* perm, EF* rowsum, hipStream_t st) {
   switch (chip) {
-    case CHIP_CPU: launch_rows<CHIP_CPU>(mainc, prepc, n, ch, perm, rows.p, st); break;
-    case CHIP_PROGRAM: launch_rows<CHIP_PROGRAM>(mainc, prepc, n, ch, perm, rows.p, st); break;
-    case CHIP_ADDSUB: launch_rows<CHIP_ADDSUB>(mainc, prepc, n, ch, perm, rows.p, st); break;
-    case CHIP_JUMP: launch_rows<CHIP_JUMP>(mainc, prepc, n, ch, perm, rows.p, st); break;
-    case CHIP_MEMORY: launch_rows<CHIP_MEMORY>(mainc, prepc, n, ch, perm, rows.p, st); break;
-    case CHIP_BYTE: launch_rows<CHIP_BYTE>(mainc, prepc, n, ch, perm, rows.p, st); break;
-    case CHIP_MEMINSTRS: launch_rows<CHIP_MEMINSTRS>(mainc, prepc, n, ch, perm, rows.p, st); break;
-    case CHIP_IO: launch_rows<CHIP_IO>(mainc, prepc, n, ch, perm, rows.p, st); break;
+    case CHIP_CPU: launch_rows<CHIP_CPU>(mainc, prepc, n, ch, perm, rowsum, st); break;
+    case CHIP_PROGRAM: launch_rows<CHIP_PROGRAM>(mainc, prepc, n, ch, perm, rowsum, st); break;
+    case CHIP_ADDSUB: launch_rows<CHIP_ADDSUB>(mainc, prepc, n, ch, perm, rowsum, st); break;
+    case CHIP_JUMP: launch_rows<CHIP_JUMP>(mainc, prepc, n, ch, perm, rowsum, st); break;
+    case CHIP_MEMORY: launch_rows<CHIP_MEMORY>(mainc, prepc, n, ch, perm, rowsum, st); break;
+    case CHIP_BYTE: launch_rows<CHIP_BYTE>(mainc, prepc, n, ch, perm, rowsum, st); break;
+    case CHIP_MEMINSTRS: launch_rows<CHIP_MEMINSTRS>(mainc, prepc, n, ch, perm, rowsum, st); break;
+    case CHIP_IO: launch_rows<CHIP_IO>(mainc, prepc, n, ch, perm, rowsum, st); break;
     default: throw std::runtime_error("perm_trace: bad chip");
   }
-  const int col0 = 4 * (perm_width(chip) - 1);
+}
+
+void perm_running_sum(const EF* rows, size_t n, uint32_t* perm, int col0, EF* cumsum_dev,
+                      hipStream_t st) {
+  const int logn = log2i(n);
+  auto last_of = [&](const EF* v, size_t count) {  // no trace wanted: the total alone
+    HIP_CHECK(hipMemcpyAsync(cumsum_dev, v + count - 1, sizeof(EF), hipMemcpyDeviceToDevice, st));
+  };
   if (logn >= PHI_LOG_MIN && phi_tiles_on()) {  // running sum by tiles of whole storage runs
     const size_t nt = (n >> 5) / PHI_Z;          // tiles per tile row
     DBuf<EF> sums(PHI_X * nt);
-    hipLaunchKernelGGL(k_phi_sums, dim3((unsigned)nt), dim3(PHI_T), 0, st, (const EF*)rows.p, logn,
-                       sums.p);
+    hipLaunchKernelGGL(k_phi_sums, dim3((unsigned)nt), dim3(PHI_T), 0, st, rows, logn, sums.p);
     KCHECK();
     ef_inclusive_scan(sums.p, PHI_X * nt, st);
-    hipLaunchKernelGGL(k_phi_write, dim3((unsigned)nt), dim3(PHI_T), 0, st, (const EF*)rows.p,
-                       logn, (const EF*)sums.p, perm, col0, cumsum_dev);
+    if (!perm) return last_of(sums.p, PHI_X * nt);
+    hipLaunchKernelGGL(k_phi_write, dim3((unsigned)nt), dim3(PHI_T), 0, st, rows, logn,
+                       (const EF*)sums.p, perm, col0, cumsum_dev);
     KCHECK();
     return;
   }
@@ -330,10 +342,11 @@ void perm_trace(int chip, const uint32_t* mainc, const uint32_t* prepc, size_t n
   // scattering phi back to bit-reversed storage
   const size_t nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
   DBuf<EF> sums(nb), nat(n);
-  hipLaunchKernelGGL(k_scan_block, dim3((unsigned)nb), dim3(SCAN_T), 0, st, (const EF*)rows.p,
-                     logn, nat.p, n, sums.p);
+  hipLaunchKernelGGL(k_scan_block, dim3((unsigned)nb), dim3(SCAN_T), 0, st, rows, logn, nat.p, n,
+                     sums.p);
   KCHECK();
   if (nb > 1) ef_inclusive_scan(sums.p, nb, st);
+  if (!perm) return last_of(sums.p, nb);
   hipLaunchKernelGGL(k_write_phi, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const EF*)nat.p, n,
                      logn, nb > 1 ? (const EF*)sums.p : nullptr, perm, col0, cumsum_dev);
   KCHECK();
