@@ -298,6 +298,20 @@ pub struct bfz_lookups_shape {
     pub _pad: i32,
 }
 
+/// The shape of a chip given as an AIR program and an interaction program (`bfz_chip_info`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bfz_chip_shape {
+    pub main_width: i32,
+    pub prep_width: i32,
+    pub perm_width: i32,
+    pub n_interactions: i32,
+    pub air_constraints: i32,
+    pub num_constraints: i32,
+    pub degree: i32,
+    pub log_quotient_degree: i32,
+}
+
 /// Limits of a BFL1 interaction program.
 pub const BFZ_LOOKUPS_MAX: usize = 32;
 pub const BFZ_LOOKUPS_MAX_VALUES: usize = 7;
@@ -506,6 +520,26 @@ extern "C" {
     pub fn bfz_lookups_time(prog: *const u8, len: usize, chip: c_int, main: *const u32,
                             prep: *const u32, height: usize, alpha: *const u32, beta: *const u32,
                             runs: c_int, prog_ms: *mut f32, chip_ms: *mut f32) -> c_int;
+
+    /// Caller-defined chips of a machine, an AIR program (optional) paired with an interaction
+    /// program: `debug_constraints` with the LogUp constraints (crates/stark/src/debug.rs:24-105)
+    /// and the chip's machine quotient (crates/stark/src/quotient.rs:18-165).
+    pub fn bfz_chip_info(air: *const u8, air_len: usize, lookups: *const u8, lookups_len: usize,
+                         out: *mut bfz_chip_shape) -> c_int;
+    pub fn bfz_chip_check_rows(air: *const u8, air_len: usize, lookups: *const u8,
+                               lookups_len: usize, main: *const u32, prep: *const u32,
+                               perm: *const u32, height: usize, alpha: *const u32,
+                               beta: *const u32, cumsum: *const u32, on_device: c_int,
+                               out: *mut bfz_chip_check, first_fail_per_row: *mut i32) -> c_int;
+    pub fn bfz_chip_quotient(chip: c_int, air: *const u8, air_len: usize, lookups: *const u8,
+                             lookups_len: usize, main: *const u32, prep: *const u32,
+                             perm: *const u32, height: usize, alpha: *const u32, beta: *const u32,
+                             cumsum_io: *mut u32, quot_alpha: *const u32, out: *mut *mut u32) -> c_int;
+    pub fn bfz_chip_quotient_time(chip: c_int, air: *const u8, air_len: usize, lookups: *const u8,
+                                  lookups_len: usize, main: *const u32, prep: *const u32,
+                                  height: usize, alpha: *const u32, beta: *const u32,
+                                  quot_alpha: *const u32, runs: c_int, prog_ms: *mut f32,
+                                  chip_ms: *mut f32) -> c_int;
 
     pub fn bfz_set_num_queries(num_queries: c_int) -> c_int;
     pub fn bfz_set_pcs_variant(observe_openings: c_int) -> c_int;

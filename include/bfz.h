@@ -808,6 +808,62 @@ int bfz_lookups_time(const uint8_t* prog, size_t len, int chip, const uint32_t* 
                      const uint32_t* prep, size_t height, const uint32_t alpha[4],
                      const uint32_t beta[4], int runs, float* prog_ms, float* chip_ms);
 
+/* ---- Caller-defined chips of a machine: an AIR program (BFA1, optional) paired with an
+ * interaction program (BFL1).  Chip::eval (crates/stark/src/chip.rs:222-228) evaluates the AIR and
+ * then the permutation constraints (crates/stark/src/permutation.rs:157-272); here both halves are
+ * data, so the row check with the LogUp constraints (debug_constraints,
+ * crates/stark/src/debug.rs:24-105) and the chip's machine quotient (quotient_values,
+ * crates/stark/src/quotient.rs:18-165) run for a chip that is not compiled in.  Constraint order
+ * and indices are bfz_check_chip's: the AIR's constraints, one per LogUp batch, then first-row,
+ * transition and last-row of the running sum; K = air_constraints + batches + 3.  Conventions are
+ * those of bfz_lookups_perm_trace: row-major Montgomery words, height a power of two in
+ * [1, 2^23], words >= p refused with the same message, air NULL / air_len 0 for a lookup-only
+ * chip (Program, Memory and Byte have that shape), prep NULL when prep_width is 0.  The pair is
+ * validated first: either program's own refusal, the AIR's width against main_width, an AIR degree
+ * above 3, and a pair without an interaction (that is an AIR alone: the bfz_air_ calls).
+ *
+ *   bfz_chip_info        host only: the pair's shape.  For a built-in chip's two exported programs
+ *                        num_constraints is the count bfz_check_chip reports.
+ *   bfz_chip_check_rows  debug_constraints of ONE caller-defined chip, with bfz_check_chip's contract
+ *                        and result struct (chip = -1).  perm: height x 4 * perm_width as
+ *                        bfz_lookups_perm_trace returns it.  on_device = 0: a single-threaded host
+ *                        path over the same two compiled lists, no device needed.
+ *   bfz_chip_quotient    the chip's machine quotient on 3 H_2n (device only).  chip >= 0 with all
+ *                        four program arguments NULL / 0 runs the compiled k_quotient<chip> (the
+ *                        yardstick); chip = -1 runs the programs (k_quotient_chip_prog).  perm =
+ *                        NULL: the permutation trace and the cumulative sum are computed on the
+ *                        device and cumsum_io is written; otherwise perm is uploaded and cumsum_io
+ *                        is read.  quot_alpha is the constraint-folding challenge.  *out (bfz_free):
+ *                        2 * height x 4 words, row i = Q(3 w_2n^i) in natural order (quotient chunk
+ *                        i mod 2, chunk row i >> 1).  Q is a polynomial of degree < 2 * height
+ *                        exactly when every constraint holds on the trace. */
+typedef struct {
+  int32_t main_width, prep_width, perm_width, n_interactions;   /* perm_width in EF columns */
+  int32_t air_constraints, num_constraints, degree, log_quotient_degree;
+} bfz_chip_shape;
+int bfz_chip_info(const uint8_t* air, size_t air_len, const uint8_t* lookups, size_t lookups_len,
+                  bfz_chip_shape* out);
+int bfz_chip_check_rows(const uint8_t* air, size_t air_len, const uint8_t* lookups,
+                        size_t lookups_len, const uint32_t* main, const uint32_t* prep,
+                        const uint32_t* perm, size_t height, const uint32_t alpha[4],
+                        const uint32_t beta[4], const uint32_t cumsum[4], int on_device,
+                        bfz_chip_check* out, int32_t* first_fail_per_row);
+int bfz_chip_quotient(int chip, const uint8_t* air, size_t air_len, const uint8_t* lookups,
+                      size_t lookups_len, const uint32_t* main, const uint32_t* prep,
+                      const uint32_t* perm, size_t height, const uint32_t alpha[4],
+                      const uint32_t beta[4], uint32_t cumsum_io[4], const uint32_t quot_alpha[4],
+                      uint32_t** out);
+
+/* Diagnostic (scripts/chip_quotient_time.py): HIP-event times, in ms, of single launches of the
+ * quotient kernels alone on one set of LDEs (the permutation trace is computed on the device),
+ * alternating after one warm-up launch of each: k_quotient_chip_prog on the programs ->
+ * prog_ms[runs] and k_quotient<chip> -> chip_ms[runs]; the programs must have that chip's shape.
+ * Nothing of the quotients comes back. */
+int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const uint8_t* lookups,
+                           size_t lookups_len, const uint32_t* main, const uint32_t* prep,
+                           size_t height, const uint32_t alpha[4], const uint32_t beta[4],
+                           const uint32_t quot_alpha[4], int runs, float* prog_ms, float* chip_ms);
+
 /* FRI_QUERIES (kb31_poseidon2.rs:59-62): 1..4096, or 0 = environment FRI_QUERIES / 84. */
 int bfz_set_num_queries(int num_queries);
 

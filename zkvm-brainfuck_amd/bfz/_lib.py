@@ -111,6 +111,13 @@ class LookupsShapeC(ctypes.Structure):
                 ("list_words", c_int32), ("_pad", c_int32)]
 
 
+class ChipShapeC(ctypes.Structure):
+    """bfz_chip_shape: the shape of a chip given as an AIR program and an interaction program."""
+    _fields_ = [("main_width", c_int32), ("prep_width", c_int32), ("perm_width", c_int32),
+                ("n_interactions", c_int32), ("air_constraints", c_int32),
+                ("num_constraints", c_int32), ("degree", c_int32), ("log_quotient_degree", c_int32)]
+
+
 class VerifyOutcomeC(ctypes.Structure):
     """bfz_verify_outcome: one proof's verdict from bfz_verify_batch."""
     _fields_ = [("ok", c_int32), ("query", c_int32), ("why", ctypes.c_char * 120)]
@@ -262,6 +269,20 @@ SIGNATURES = [
     ("bfz_lookups_time", c_int, [POINTER(c_uint8), c_size_t, c_int, POINTER(c_uint32),
                                  POINTER(c_uint32), c_size_t, POINTER(c_uint32), POINTER(c_uint32),
                                  c_int, POINTER(ctypes.c_float), POINTER(ctypes.c_float)]),
+    ("bfz_chip_info", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint8), c_size_t,
+                              POINTER(ChipShapeC)]),
+    ("bfz_chip_check_rows", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint8), c_size_t,
+                                    POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
+                                    c_size_t, POINTER(c_uint32), POINTER(c_uint32),
+                                    POINTER(c_uint32), c_int, POINTER(ChipCheck), POINTER(c_int32)]),
+    ("bfz_chip_quotient", c_int, [c_int, POINTER(c_uint8), c_size_t, POINTER(c_uint8), c_size_t,
+                                  POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32), c_size_t,
+                                  POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
+                                  POINTER(c_uint32), POINTER(POINTER(c_uint32))]),
+    ("bfz_chip_quotient_time", c_int, [c_int, POINTER(c_uint8), c_size_t, POINTER(c_uint8), c_size_t,
+                                       POINTER(c_uint32), POINTER(c_uint32), c_size_t,
+                                       POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
+                                       c_int, POINTER(ctypes.c_float), POINTER(ctypes.c_float)]),
     ("bfz_set_num_queries", c_int, [c_int]),
     ("bfz_set_pcs_variant", c_int, [c_int]),
     ("bfz_set_fault_injection", c_int, [c_int]),

@@ -1485,6 +1485,118 @@ def lookups_balance(progs, mains, preps, alpha, beta, on_device: bool = True) ->
     return LookupsBalance(bool(ok.value), list(total), [list(cums[4 * i:4 * i + 4]) for i in range(k)])
 
 
+# ---- caller-defined chips of a machine: an AIR program paired with an interaction program
+@dataclass
+class ChipInfo:
+    """bfz_chip_shape: perm_width in EF columns; num_constraints = air_constraints + batches + 3."""
+    main_width: int
+    prep_width: int
+    perm_width: int
+    n_interactions: int
+    air_constraints: int
+    num_constraints: int
+    degree: int
+    log_quotient_degree: int
+
+
+def _chip_progs(air, lookups):
+    a, an = u8buf(air) if air else (None, 0)
+    lk, ln = u8buf(lookups) if lookups else (None, 0)
+    return a, an, lk, ln
+
+
+def chip_info(air: Optional[bytes], lookups: bytes) -> ChipInfo:
+    """bfz_chip_info (host only): validates the pair (air = None: a lookup-only chip) and returns
+    its shape; raises BfzError naming what is wrong."""
+    a, an, lk, ln = _chip_progs(air, lookups)
+    out = _lib.ChipShapeC()
+    check(lib().bfz_chip_info(a, an, lk, ln, ctypes.byref(out)))
+    return ChipInfo(out.main_width, out.prep_width, out.perm_width, out.n_interactions,
+                    out.air_constraints, out.num_constraints, out.degree, out.log_quotient_degree)
+
+
+def _chip_traces(info: ChipInfo, main, prep, perm, what):
+    main, prep = _lookups_chip_args(info, main, prep, what)
+    perm = _lookups_trace(perm, what)
+    if perm is not None and perm.shape != (main.shape[0], 4 * info.perm_width):
+        raise ValueError(f"{what}: the permutation trace must be "
+                         f"({main.shape[0]}, {4 * info.perm_width})")
+    return main, prep, perm
+
+
+def chip_check(air: Optional[bytes], lookups: bytes, main, prep, perm, alpha, beta, cumsum,
+               on_device: bool = True, per_row: bool = False) -> ChipCheckResult:
+    """bfz_chip_check_rows: debug_constraints (crates/stark/src/debug.rs:24-105) of one
+    caller-defined chip -- the AIR's constraints, one per LogUp batch, then the running sum's
+    first-row, transition and last-row constraints.  Arguments as check_chip, perm as
+    lookups_perm_trace returns it; the result's chip is -1."""
+    import numpy as np
+    if on_device:
+        init()
+    main, prep, perm = _chip_traces(chip_info(air, lookups), main, prep, perm, "chip_check")
+    if perm is None:
+        raise ValueError("chip_check: needs the permutation trace")
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    a, an, lk, ln = _chip_progs(air, lookups)
+    out = _lib.ChipCheck()
+    rows = np.zeros(main.shape[0], dtype=np.int32) if per_row else None
+    check(lib().bfz_chip_check_rows(
+        a, an, lk, ln, main.ctypes.data_as(u32p),
+        prep.ctypes.data_as(u32p) if prep is not None else None, perm.ctypes.data_as(u32p),
+        main.shape[0], (ctypes.c_uint32 * 4)(*alpha), (ctypes.c_uint32 * 4)(*beta),
+        (ctypes.c_uint32 * 4)(*cumsum), int(bool(on_device)), ctypes.byref(out),
+        rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if per_row else None))
+    return _chip_result(out, rows)
+
+
+def chip_quotient(air: Optional[bytes], lookups: Optional[bytes], main, prep, alpha, beta,
+                  quot_alpha, perm=None, cumsum=None, chip: int = -1):
+    """bfz_chip_quotient (device): the chip's machine quotient (quotient_values,
+    crates/stark/src/quotient.rs:18-165) on 3 H_2n.  chip = -1 runs the two programs; chip >= 0
+    (air = lookups = None) runs that built-in chip's compiled kernel.  perm = None: the
+    permutation trace and cumulative sum are computed on the device; otherwise both are the
+    caller's.  Returns (q, cumsum): q is (2 * height, 4) Montgomery words, row i = Q(3 w_2n^i)."""
+    import numpy as np
+    init()
+    if chip >= 0:
+        info = ChipInfo(_MAIN_W[chip], _PREP_W[chip], _PERM_W[chip] // 4, 0, 0, 0, 3, 1)
+    else:
+        info = chip_info(air, lookups)
+    main, prep, perm = _chip_traces(info, main, prep, perm, "chip_quotient")
+    if perm is not None and cumsum is None:
+        raise ValueError("chip_quotient: a caller's permutation trace needs its cumulative sum")
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    a, an, lk, ln = _chip_progs(air, lookups)
+    cs = (ctypes.c_uint32 * 4)(*(cumsum if perm is not None else [0, 0, 0, 0]))
+    out = u32p()
+    check(lib().bfz_chip_quotient(
+        int(chip), a, an, lk, ln, main.ctypes.data_as(u32p),
+        prep.ctypes.data_as(u32p) if prep is not None else None,
+        perm.ctypes.data_as(u32p) if perm is not None else None, main.shape[0],
+        (ctypes.c_uint32 * 4)(*alpha), (ctypes.c_uint32 * 4)(*beta), cs,
+        (ctypes.c_uint32 * 4)(*quot_alpha), ctypes.byref(out)))
+    q = np.ctypeslib.as_array(out, shape=(2 * main.shape[0], 4)).copy()
+    lib().bfz_free(out)
+    return q, list(cs)
+
+
+def chip_quotient_time(chip: int, air: Optional[bytes], lookups: bytes, main, prep, alpha, beta,
+                       quot_alpha, runs: int = 20):
+    """bfz_chip_quotient_time (diagnostic): per-launch HIP-event milliseconds of
+    k_quotient_chip_prog on the programs and of k_quotient<chip>, alternating, `runs` each."""
+    init()
+    main, prep, _ = _chip_traces(chip_info(air, lookups), main, prep, None, "chip_quotient_time")
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    a, an, lk, ln = _chip_progs(air, lookups)
+    pm, cm = (ctypes.c_float * runs)(), (ctypes.c_float * runs)()
+    check(lib().bfz_chip_quotient_time(
+        int(chip), a, an, lk, ln, main.ctypes.data_as(u32p),
+        prep.ctypes.data_as(u32p) if prep is not None else None, main.shape[0],
+        (ctypes.c_uint32 * 4)(*alpha), (ctypes.c_uint32 * 4)(*beta),
+        (ctypes.c_uint32 * 4)(*quot_alpha), int(runs), pm, cm))
+    return list(pm), list(cm)
+
+
 def set_num_queries(q: int) -> None:
     """FRI_QUERIES override (crates/stark/src/kb31_poseidon2.rs:59-62); 0 = environment/84."""
     check(lib().bfz_set_num_queries(int(q)))

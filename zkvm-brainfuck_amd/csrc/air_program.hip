@@ -12,6 +12,7 @@
 // does not depend on the order the compiled template or this interpreter evaluates it in.
 #include "air_program.h"
 
+#include "air_program_dev.h"
 #include "debug_check.h"
 #include "quotient.h"
 
@@ -19,47 +20,7 @@ namespace bfz {
 
 using namespace kb;
 
-namespace {
-using ConstWords = const __attribute__((address_space(4))) uint32_t*;
-
-// mainc: the column-major matrix (stride words per column); vt / vn: the byte offsets of the
-// thread's local and next position in a column.
-template <class Sink>
-__device__ __forceinline__ void run_program(ConstWords code, int ncode,
-                                            uint32_t (*slots)[256], const uint32_t* mainc,
-                                            size_t stride, uint32_t vt, uint32_t vn,
-                                            uint32_t first, uint32_t last, uint32_t trans,
-                                            Sink& sink) {
-  const uint32_t tid = threadIdx.x;
-  for (int pc = 0; pc < ncode;) {
-    const uint32_t w = code[pc++];
-    const uint32_t d = (w >> 8) & 0xff, a = (w >> 16) & 0xff, b = w >> 24;
-    switch (w & 0xff) {
-      case AIR_CONST: slots[d][tid] = code[pc++]; break;
-      case AIR_LOCAL: slots[d][tid] = ld_b(rsrc_of(mainc + (size_t)a * stride), vt, 0); break;
-      case AIR_NEXT: slots[d][tid] = ld_b(rsrc_of(mainc + (size_t)a * stride), vn, 0); break;
-      case AIR_FIRST: slots[d][tid] = first; break;
-      case AIR_LAST: slots[d][tid] = last; break;
-      case AIR_TRANS: slots[d][tid] = trans; break;
-      case AIR_ADD: slots[d][tid] = madd(slots[a][tid], slots[b][tid]); break;
-      case AIR_SUB: slots[d][tid] = msub(slots[a][tid], slots[b][tid]); break;
-      case AIR_MUL: slots[d][tid] = mmul(slots[a][tid], slots[b][tid]); break;
-      case AIR_NEG: slots[d][tid] = mneg(slots[a][tid]); break;
-      default: sink.emit(slots[a][tid]);  // AIR_EMIT
-    }
-  }
-}
-
-// The row check's sink: counts the emissions, keeps the first that is not zero and ignores the
-// rest (FirstFailAcc; the loop stays wave-uniform).
-struct FirstFailSink {
-  int n = 0, first = -1;
-  __device__ __forceinline__ void emit(uint32_t c) {
-    if (c != 0 && first < 0) first = n;
-    n++;
-  }
-};
-}  // namespace
+// run_program<Sink> and FirstFailSink are in air_program_dev.h (chip_program.hip runs them too).
 
 template <int LQD>
 __global__ __launch_bounds__(256) void k_quotient_prog(const uint32_t* __restrict__ code, int ncode,

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/bfz.h"
+#include "chip_program.h"
 #include "debug_check.h"
 #include "fri.h"
 #include "logup.h"
@@ -1654,6 +1655,278 @@ int bfz_lookups_time(const uint8_t* prog, size_t len, int chip, const uint32_t* 
       if (r >= 0) {
         prog_ms[r] = a;
         if (chip >= 0) chip_ms[r] = b;
+      }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return 0;
+  });
+}
+
+// ---- caller-defined chips of a machine: an AIR program paired with an interaction program
+// (chip_program.h)
+}  // extern "C"
+namespace {
+// One chip's quotient inputs on the device: the pair's lists (chip = -1) or a built-in chip, the
+// traces uploaded, the permutation trace computed or uploaded, the three coset LDEs on 3 H_2n
+// (shift 3, as commit_lde), the alpha powers and the quotient parameters, all on one stream.
+struct ChipQuotSetup {
+  int chip;
+  bfz::ChipProgram p;  // chip = -1
+  int mw, pw, permw, K;
+  size_t n;
+  bfz::DBuf<uint32_t> code, list, lm, lp, le, qout;
+  bfz::DBuf<kb::EF> apows;
+  bfz::DBuf<bfz::QuotParams> qpd;
+  bfz::QuotParams qp;
+  kb::EF cumsum;
+
+  ChipQuotSetup(int chip_, const uint8_t* air, size_t air_len, const uint8_t* lookups,
+                size_t lookups_len, const uint32_t* main, const uint32_t* prep, const uint32_t* perm,
+                size_t height, const uint32_t alpha[4], const uint32_t beta[4],
+                const uint32_t cumsum_in[4], const uint32_t quot_alpha[4], hipStream_t st)
+      : chip(chip_), n(height) {
+    if (!main || !alpha || !beta || !quot_alpha) throw std::runtime_error("null argument");
+    if (chip < -1 || chip >= bfz::NUM_CHIPS) throw std::runtime_error("bad chip index");
+    if (chip >= 0) {
+      if (air || air_len || lookups || lookups_len)
+        throw std::runtime_error("chip_quotient: a built-in chip (chip >= 0) takes no programs");
+      mw = bfz::CHIP_INFO[chip].main_w;
+      pw = bfz::CHIP_INFO[chip].prep_w;
+      permw = bfz::perm_width(chip);
+      K = bfz::num_constraints(chip);
+    } else {
+      p = bfz::chip_compile(air, air_len, lookups, lookups_len);
+      mw = p.lk.main_w;
+      pw = p.lk.prep_w;
+      permw = p.perm_width();
+      K = p.num_constraints();
+    }
+    if (n == 0 || (n & (n - 1)) || n > ((size_t)1 << 23))
+      throw std::runtime_error("chip_quotient: height not a power of two in [1, 2^23]");
+    if (pw && !prep) throw std::runtime_error("chip_quotient: the chip has preprocessed columns");
+    const bfz::PermChallenges ch = lookup_challenges(alpha, beta);
+    const kb::EF qa = ef_arg(quot_alpha, "challenge");
+    if (perm) cumsum = ef_arg(cumsum_in, "cumulative sum");
+
+    const bfz::DBuf<uint32_t> mc = bfz::uni_upload_trace((size_t)mw, "chip", main, n, st);
+    bfz::DBuf<uint32_t> pc, pe;
+    if (pw) pc = bfz::uni_upload_trace((size_t)pw, "chip", prep, n, st);
+    if (chip < 0) {
+      list.reset(p.lk.list.size());
+      bfz::upload_async(list.p, p.lk.list.data(), p.lk.list.size() * 4, st);
+      if (p.has_air) {
+        code.reset(p.air.code.size());
+        bfz::upload_async(code.p, p.air.code.data(), p.air.code.size() * 4, st);
+      }
+    }
+    if (perm) {
+      pe = bfz::uni_upload_trace(4 * (size_t)permw, "chip", perm, n, st);
+    } else {
+      pe.reset(n * 4 * (size_t)permw);
+      bfz::DBuf<bfz::PermChallenges> chd(1);
+      bfz::DBuf<kb::EF> csd(1);
+      bfz::upload_async(chd.p, &ch, sizeof(ch), st);
+      if (chip >= 0) bfz::perm_trace(chip, mc.p, pw ? pc.p : nullptr, n, chd.p, pe.p, csd.p, st);
+      else bfz::perm_trace_prog(p.lk, list.p, mc.p, pw ? pc.p : nullptr, n, chd.p, pe.p, csd.p, st);
+      HIP_CHECK(hipMemcpyAsync(&cumsum, csd.p, sizeof(cumsum), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    }
+    const uint32_t three = kb::to_mont(3);  // GENERATOR / the trace domain's shift 1
+    lm.reset(2 * n * (size_t)mw);
+    bfz::coset_lde(mc.p, n, mw, three, lm.p, st);
+    if (pw) {
+      lp.reset(2 * n * (size_t)pw);
+      bfz::coset_lde(pc.p, n, pw, three, lp.p, st);
+    }
+    le.reset(2 * n * 4 * (size_t)permw);
+    bfz::coset_lde(pe.p, n, 4 * permw, three, le.p, st);
+
+    std::vector<kb::EF> ap((size_t)K);  // alpha^(K-1-k): the Horner fold as a sum (quotient.hip)
+    kb::EF pwr = kb::ef_one();
+    for (int k = K - 1; k >= 0; k--) {
+      ap[k] = pwr;
+      pwr = kb::ef_mul(pwr, qa);
+    }
+    apows.reset((size_t)K);
+    bfz::upload_async(apows.p, ap.data(), (size_t)K * sizeof(kb::EF), st);
+    qp = bfz::quot_params_of_height(n, apows.p);
+    qp.perm_alpha = ch.alpha;
+    for (int j = 0; j < 8; j++) qp.beta_pows[j] = ch.beta_pows[j];
+    qp.cumsum = cumsum;
+    qpd.reset(1);
+    bfz::upload_async(qpd.p, &qp, sizeof(qp), st);
+    qout.reset(8 * n);
+    HIP_CHECK(hipStreamSynchronize(st));  // the uploads' host sources end with this constructor
+  }
+
+  // One launch of the quotient kernel: the compiled template of `chip`, or the programs'.
+  void launch(bool compiled, hipStream_t st) {
+    const int logN = bfz::log2i(n) + 1;
+    const bfz::QuotOut qo{{qout.p, qout.p + 4 * n}, n};
+    if (compiled) {
+      bfz::QuotRows in{lm.p, lm.p, le.p, le.p, pw ? lp.p : nullptr, 2 * n, 0, 2 * n, {}, {}};
+      for (int c = 0; c < 64; c++) in.nmain[c] = in.nperm[c] = (uint8_t)c;
+      bfz::quotient_into(chip, in, logN, qp, qo, st, qpd.p);
+    } else {
+      const bfz::ChipLists cl{p.has_air ? code.p : nullptr, p.has_air ? (int)p.air.code.size() : 0,
+                              list.p, p.air_constraints(), p.num_constraints()};
+      bfz::quotient_chip_prog(cl, lm.p, pw ? lp.p : nullptr, le.p, logN, qp, qpd.p, qo, st);
+    }
+  }
+};
+
+bfz::ChipLists chip_lists(const bfz::ChipProgram& p, const uint32_t* code, const uint32_t* list) {
+  return bfz::ChipLists{p.has_air ? code : nullptr, p.has_air ? (int)p.air.code.size() : 0, list,
+                        p.air_constraints(), p.num_constraints()};
+}
+}  // namespace
+extern "C" {
+
+int bfz_chip_info(const uint8_t* air, size_t air_len, const uint8_t* lookups, size_t lookups_len,
+                  bfz_chip_shape* out) {
+  return guarded([&] {
+    if (!out) throw std::runtime_error("null argument");
+    const bfz::ChipProgram p = bfz::chip_compile(air, air_len, lookups, lookups_len);
+    static_assert(sizeof(bfz_chip_shape) == 32, "bfz_chip_shape has no gaps");
+    std::memset(out, 0, sizeof *out);
+    out->main_width = p.lk.main_w;
+    out->prep_width = p.lk.prep_w;
+    out->perm_width = p.perm_width();
+    out->n_interactions = p.lk.n;
+    out->air_constraints = p.air_constraints();
+    out->num_constraints = p.num_constraints();
+    out->degree = p.degree();
+    out->log_quotient_degree = p.log_quotient_degree();
+    return 0;
+  });
+}
+
+int bfz_chip_check_rows(const uint8_t* air, size_t air_len, const uint8_t* lookups,
+                        size_t lookups_len, const uint32_t* main, const uint32_t* prep,
+                        const uint32_t* perm, size_t height, const uint32_t alpha[4],
+                        const uint32_t beta[4], const uint32_t cumsum[4], int on_device,
+                        bfz_chip_check* out, int32_t* first_fail_per_row) {
+  return guarded([&] {
+    if (!perm || !alpha || !beta || !cumsum || !out) throw std::runtime_error("null argument");
+    const bfz::ChipProgram p = bfz::chip_compile(air, air_len, lookups, lookups_len);
+    lookup_dims_or_throw(p.lk, main, prep, height);
+    const bfz::PermChallenges ch = lookup_challenges(alpha, beta);
+    const kb::EF cs = ef_arg(cumsum, "cumulative sum");
+    const size_t w = 4 * (size_t)p.perm_width(), n = height;
+    bfz::ChipCheck cc;
+    if (!on_device) {
+      lookup_canonical_or_throw(p.lk, main, prep, n);
+      for (size_t i = 0; i < n * w; i++)
+        if (perm[i] >= kb::P) bfz::uni_noncanonical_throw("chip");
+      bfz::chip_check_host(p, main, prep, perm, n, ch, cs, cc, first_fail_per_row);
+      to_c(cc, out);
+      return 0;
+    }
+    hipStream_t st = bfz::stream();
+    const bfz::DBuf<uint32_t> mc = bfz::uni_upload_trace((size_t)p.lk.main_w, "chip", main, n, st);
+    const bfz::DBuf<uint32_t> pe = bfz::uni_upload_trace(w, "chip", perm, n, st);
+    bfz::DBuf<uint32_t> pc;
+    if (p.lk.prep_w) pc = bfz::uni_upload_trace((size_t)p.lk.prep_w, "chip", prep, n, st);
+    bfz::DBuf<uint32_t> list(p.lk.list.size()), code(p.has_air ? p.air.code.size() : 1);
+    bfz::upload_async(list.p, p.lk.list.data(), p.lk.list.size() * 4, st);
+    if (p.has_air) bfz::upload_async(code.p, p.air.code.data(), p.air.code.size() * 4, st);
+    bfz::DBuf<bfz::PermChallenges> chd(1);
+    bfz::DBuf<kb::EF> csd(1);
+    bfz::DBuf<unsigned long long> resd(2);
+    bfz::DBuf<int32_t> rowd;
+    if (first_fail_per_row) rowd.reset(n);
+    unsigned long long res[2] = {~0ull, 0};
+    bfz::upload_async(chd.p, &ch, sizeof(ch), st);
+    bfz::upload_async(csd.p, &cs, sizeof(cs), st);
+    bfz::upload_async(resd.p, res, sizeof(res), st);
+    bfz::check_chip_prog_device(chip_lists(p, code.p, list.p), mc.p, p.lk.prep_w ? pc.p : nullptr,
+                                pe.p, n, chd.p, csd.p, resd.p,
+                                first_fail_per_row ? rowd.p : nullptr, st);
+    std::vector<int32_t> rows(first_fail_per_row ? n : 0);
+    HIP_CHECK(hipMemcpyAsync(res, resd.p, sizeof(res), hipMemcpyDeviceToHost, st));
+    if (first_fail_per_row)
+      HIP_CHECK(hipMemcpyAsync(rows.data(), rowd.p, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    bfz::staging_reset();
+    cc.height = n;
+    cc.num_constraints = p.num_constraints();
+    cc.num_batches = p.lk.batches();
+    cc.cumsum = cs;
+    bfz::decode_check_result(res, cc);
+    if (first_fail_per_row) {
+      const int logh = bfz::log2i(n);
+      for (size_t r = 0; r < n; r++)  // storage position -> natural row
+        first_fail_per_row[r] = rows[bfz::bitrev32((uint32_t)r, logh)];
+    }
+    to_c(cc, out);
+    return 0;
+  });
+}
+
+int bfz_chip_quotient(int chip, const uint8_t* air, size_t air_len, const uint8_t* lookups,
+                      size_t lookups_len, const uint32_t* main, const uint32_t* prep,
+                      const uint32_t* perm, size_t height, const uint32_t alpha[4],
+                      const uint32_t beta[4], uint32_t cumsum_io[4], const uint32_t quot_alpha[4],
+                      uint32_t** out) {
+  return guarded([&] {
+    if (!cumsum_io || !out) throw std::runtime_error("null argument");
+    hipStream_t st = bfz::stream();
+    ChipQuotSetup s(chip, air, air_len, lookups, lookups_len, main, prep, perm, height, alpha, beta,
+                    cumsum_io, quot_alpha, st);
+    bfz::staging_reset();
+    s.launch(chip >= 0, st);
+    const size_t n = height;
+    std::vector<uint32_t> q(8 * n);  // chunk c, component e at q[(4 c + e) n + position]
+    HIP_CHECK(hipMemcpyAsync(q.data(), s.qout.p, q.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    bfz::staging_reset();
+    uint32_t* o = (uint32_t*)std::malloc(8 * n * 4 + 4);
+    if (!o) throw std::runtime_error("out of host memory");
+    const int logN = bfz::log2i(n) + 1;
+    for (size_t i = 0; i < 2 * n; i++) {  // storage position t = bitrev(i): chunk t >> log n
+      const size_t t = bfz::bitrev32((uint32_t)i, logN), c = t / n, pos = t & (n - 1);
+      for (int e = 0; e < 4; e++) o[4 * i + e] = q[(4 * c + e) * n + pos];
+    }
+    std::memcpy(cumsum_io, s.cumsum.c, 16);
+    *out = o;
+    return 0;
+  });
+}
+
+int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const uint8_t* lookups,
+                           size_t lookups_len, const uint32_t* main, const uint32_t* prep,
+                           size_t height, const uint32_t alpha[4], const uint32_t beta[4],
+                           const uint32_t quot_alpha[4], int runs, float* prog_ms, float* chip_ms) {
+  return guarded([&] {
+    if (!prog_ms || !chip_ms) throw std::runtime_error("null argument");
+    if (chip < 0 || chip >= bfz::NUM_CHIPS || runs < 1)
+      throw std::runtime_error("chip_quotient_time: bad chip or run count");
+    hipStream_t st = bfz::stream();
+    ChipQuotSetup s(-1, air, air_len, lookups, lookups_len, main, prep, nullptr, height, alpha, beta,
+                    nullptr, quot_alpha, st);
+    bfz::staging_reset();
+    if (s.mw != bfz::CHIP_INFO[chip].main_w || s.pw != bfz::CHIP_INFO[chip].prep_w ||
+        s.permw != bfz::perm_width(chip) || s.K != bfz::num_constraints(chip))
+      throw std::runtime_error("chip_quotient_time: the programs do not have the chip's shape");
+    s.chip = chip;
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    auto timed = [&](bool compiled) {
+      HIP_CHECK(hipEventRecord(e0, st));
+      s.launch(compiled, st);
+      HIP_CHECK(hipEventRecord(e1, st));
+      HIP_CHECK(hipEventSynchronize(e1));
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      return ms;
+    };
+    for (int r = -1; r < runs; r++) {  // r = -1: the warm-up launches
+      const float a = timed(false), b = timed(true);
+      if (r >= 0) {
+        prog_ms[r] = a;
+        chip_ms[r] = b;
       }
     }
     (void)hipEventDestroy(e0);

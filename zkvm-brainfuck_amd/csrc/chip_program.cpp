@@ -1,0 +1,109 @@
+// Chip programs on the host (chip_program.h): the pairing of the two programs and the
+// single-threaded row check.
+#include "chip_program.h"
+
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
+namespace bfz {
+
+using namespace kb;
+
+ChipProgram chip_compile(const uint8_t* air, size_t air_len, const uint8_t* lookups,
+                         size_t lookups_len) {
+  const char* no_lookups =
+      "chip program: no interactions -- a chip without lookups is an AIR alone (bfz_air_*)";
+  if (!lookups || lookups_len == 0) throw std::runtime_error(no_lookups);
+  if (lookups_len >= 16) {  // a well-formed header that declares none: the same message
+    uint32_t magic, n;
+    std::memcpy(&magic, lookups, 4);
+    std::memcpy(&n, lookups + 12, 4);
+    if (magic == LKP_MAGIC && n == 0) throw std::runtime_error(no_lookups);
+  }
+  ChipProgram p;
+  p.lk = lookups_compile(lookups, lookups_len);
+  p.has_air = air != nullptr && air_len != 0;
+  if (p.has_air) {
+    p.air = air_compile(air, air_len);  // (refuses a degree above 3 itself)
+    if (p.air.degree > 3)
+      throw std::runtime_error("chip program: AIR degree " + std::to_string(p.air.degree) +
+                               " is above 3 (log quotient degree 1)");
+    if (p.air.width != p.lk.main_w)
+      throw std::runtime_error("chip program: the AIR's width " + std::to_string(p.air.width) +
+                               " is not the interactions' main width " +
+                               std::to_string(p.lk.main_w));
+  }
+  return p;
+}
+
+namespace {
+struct HostFail {  // FirstFailAcc continued after the AIR's constraints
+  int n, first = -1;
+  void emit_ext(const EF& c) {
+    if (!ef_is_zero(c) && first < 0) first = n;
+    n++;
+  }
+};
+EF ef_at(const uint32_t* w) {
+  EF e;
+  std::memcpy(e.c, w, 16);
+  return e;
+}
+}  // namespace
+
+void chip_check_host(const ChipProgram& p, const uint32_t* main, const uint32_t* prep,
+                     const uint32_t* perm, size_t h, const PermChallenges& ch, const EF& cumsum,
+                     ChipCheck& out, int32_t* per_row) {
+  if (h < 1 || (h & (h - 1)) || h > ((size_t)1 << 23))
+    throw std::runtime_error("chip program: height not a power of two in [1, 2^23]");
+  if (p.lk.prep_w && !prep) throw std::runtime_error("chip program: the chip has preprocessed columns");
+  const int mw = p.lk.main_w, pw = p.lk.prep_w, nb = p.lk.batches(), ni = p.lk.n;
+  const size_t w = 4 * (size_t)p.perm_width();
+  const uint32_t* list = p.lk.list.data();
+  out = ChipCheck{};
+  out.height = h;
+  out.num_constraints = p.num_constraints();
+  out.num_batches = nb;
+  out.cumsum = cumsum;
+  for (size_t i = 0; i < h; i++) {
+    const size_t nx = (i + 1) & (h - 1);
+    const bool is_first = i == 0, is_last = i == h - 1;
+    const uint32_t* m = main + i * (size_t)mw;
+    int idx = p.has_air ? air_first_fail(p.air, m, main + nx * (size_t)mw, is_first, is_last) : -1;
+    if (idx < 0) {
+      const uint32_t* pr = pw ? prep + i * (size_t)pw : nullptr;
+      const uint32_t *pl = perm + i * w, *pn = perm + nx * w;
+      HostFail acc{p.air_constraints()};
+      EF sum_l = ef_zero(), sum_n = ef_zero();
+      size_t at = LKP_HEAD;
+      for (int b = 0; b < nb; b++) {
+        EF d0, d1;
+        uint32_t m0, m1;
+        host_interaction(list, at, m, pr, ch, d0, m0);
+        const EF v = ef_at(pl + 4 * b);
+        if (2 * b + 1 < ni) {
+          host_interaction(list, at, m, pr, ch, d1, m1);
+          acc.emit_ext(ef_sub(ef_mul(ef_mul(d0, d1), v),
+                              ef_add(ef_mul_base(d1, m0), ef_mul_base(d0, m1))));
+        } else {
+          acc.emit_ext(ef_sub(ef_mul(d0, v), ef_base(m0)));
+        }
+        sum_l = ef_add(sum_l, v);
+        sum_n = ef_add(sum_n, ef_at(pn + 4 * b));
+      }
+      const EF phi_l = ef_at(pl + 4 * nb), phi_n = ef_at(pn + 4 * nb);
+      acc.emit_ext(is_first ? ef_sub(phi_l, sum_l) : ef_zero());
+      acc.emit_ext(is_last ? ef_zero() : ef_sub(ef_sub(phi_n, phi_l), sum_n));
+      acc.emit_ext(is_last ? ef_sub(phi_l, cumsum) : ef_zero());
+      idx = acc.first;
+    }
+    if (per_row) per_row[i] = idx;
+    if (idx >= 0 && out.failing_rows++ == 0) {
+      out.first_row = (int64_t)i;
+      out.first_constraint = idx;
+    }
+  }
+}
+
+}  // namespace bfz

@@ -119,6 +119,7 @@ uint32_t host_vcol(const uint32_t* list, size_t& at, const uint32_t* m, const ui
   }
   return r;
 }
+}  // namespace
 // The interaction at list[at]: its denominator and signed multiplicity.
 void host_interaction(const uint32_t* list, size_t& at, const uint32_t* m, const uint32_t* pr,
                       const PermChallenges& ch, EF& den, uint32_t& mult) {
@@ -130,7 +131,6 @@ void host_interaction(const uint32_t* list, size_t& at, const uint32_t* m, const
   for (uint32_t v = 0; v < nv; v++)
     den = ef_add(den, ef_mul_base(ch.beta_pows[v + 1], host_vcol(list, at, m, pr)));
 }
-}  // namespace
 
 void lookups_perm_trace_host(const LookupProgram& p, const uint32_t* main, const uint32_t* prep,
                              size_t h, const PermChallenges& ch, uint32_t* out, EF* cumsum) {

@@ -56,6 +56,12 @@ std::vector<uint8_t> lookups_export(int chip);
 void lookups_perm_trace_host(const LookupProgram& p, const uint32_t* main, const uint32_t* prep,
                              size_t h, const PermChallenges& ch, uint32_t* out, kb::EF* cumsum);
 
+// The host loop's step, for other host loops over a compiled list (chip_program.cpp): the
+// interaction at list[at] over one row (m / pr: its main and preprocessed words), its denominator
+// and signed multiplicity (a receive's negated); at advances past it.
+void host_interaction(const uint32_t* list, size_t& at, const uint32_t* m, const uint32_t* pr,
+                      const PermChallenges& ch, kb::EF& den, uint32_t& mult);
+
 // ---- device side (lookup_program.hip).  list_dev: the compiled list in device memory; mainc /
 // prepc: column-major bit-reversed traces of n rows; ch: device memory.  perm: 4 * perm_width()
 // base columns, or nullptr: the cumulative sum alone (k_perm_rows_prog<0>, nothing of a

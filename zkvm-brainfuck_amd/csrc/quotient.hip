@@ -19,6 +19,7 @@
 
 #include "air.h"
 #include "air_program.h"
+#include "chip_program.h"
 
 namespace bfz {
 
@@ -269,6 +270,18 @@ void quotient_prog(const uint32_t* code_dev, int ncode, int lqd, const uint32_t*
   const uint32_t* sel = sel_inv_table(logN, qp, st);
   launch_quotient_prog(lqd, code_dev, ncode, mainc, logN, qp_dev, (const uint32_t*)twiddles().fwd(),
                        sel, qout, st);
+}
+
+// The machine quotient of a chip that arrives as a pair of programs (chip_program.h): the same
+// tables, k_quotient_chip_prog<has AIR> instead of k_quotient<CHIP>.
+void quotient_chip_prog(const ChipLists& cl, const uint32_t* mainc, const uint32_t* prepc,
+                        const uint32_t* permc, int logN, const QuotParams& qp,
+                        const QuotParams* qp_dev, const QuotOut& qout, hipStream_t st) {
+  if (logN < 1 || logN > 24) throw std::runtime_error("quotient_chip_prog: bad LDE height");
+  twiddles().ensure(logN);
+  const uint32_t* sel = sel_inv_table(logN, qp, st);
+  launch_quotient_chip_prog(cl, mainc, prepc, permc, logN, qp_dev,
+                            (const uint32_t*)twiddles().fwd(), sel, qout, st);
 }
 
 // The quotient challenge on the device (challenger.h): the sponge observes the permutation
