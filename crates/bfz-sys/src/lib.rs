@@ -284,6 +284,47 @@ pub struct bfz_air_shape {
     pub _pad: i32,
 }
 
+/// A lookup key of caller-defined chips whose sends and receives differ (`bfz_lookups_debug`);
+/// the chips' shares are side arrays of `n_chips` words per record.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bfz_lookups_discrepancy {
+    pub kind: i32,
+    pub nvals: i32,
+    pub values: [u32; 7],
+    pub net: i32,
+    pub first_chip: i32,
+    pub first_interaction: i32,
+    pub first_row: i64,
+}
+
+/// `bfz_lookup_report` with `chip_distinct` as the caller's array of `n_chips` words.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bfz_lookups_report {
+    pub balanced: i32,
+    pub total_net: i32,
+    pub interactions: u64,
+    pub distinct_keys: u64,
+    pub unbalanced_keys: u64,
+    pub chip_distinct: *mut u64,
+    pub n_written: u32,
+    pub rounds: u32,
+    pub tag_collisions: u32,
+    pub _pad: u32,
+    pub table_bytes: u64,
+}
+
+/// The outcome of `bfz_lookups_multiplicities`; `first` is valid when `unmatched > 0`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct bfz_lookups_mult_report {
+    pub interactions: u64,
+    pub distinct_keys: u64,
+    pub unmatched: u64,
+    pub first: bfz_lookups_discrepancy,
+}
+
 /// The shape of an interaction program and the size of its compiled list (`bfz_lookups_info`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -516,6 +557,23 @@ extern "C" {
                                heights: *const usize, n_chips: usize, alpha: *const u32,
                                beta: *const u32, on_device: c_int, cumsums: *mut u32,
                                total: *mut u32, balanced: *mut c_int) -> c_int;
+
+    /// `debug_interactions_with_all_chips` (crates/stark/src/lookup/debug.rs:59-196) for
+    /// caller-defined chips, and the multiplicity column of a table chip from its senders.
+    pub fn bfz_lookups_debug(progs: *const *const u8, lens: *const usize,
+                             mains: *const *const u32, preps: *const *const u32,
+                             heights: *const usize, n_chips: usize, kinds: *const u32,
+                             n_kinds: usize, on_device: c_int, report: *mut bfz_lookups_report,
+                             out: *mut bfz_lookups_discrepancy, chip_net: *mut i32,
+                             chip_count: *mut u32, cap: usize) -> c_int;
+    pub fn bfz_lookups_multiplicities(table_prog: *const u8, table_len: usize,
+                                      table_main: *const u32, table_prep: *const u32,
+                                      table_height: usize, interaction: c_int,
+                                      progs: *const *const u8, lens: *const usize,
+                                      mains: *const *const u32, preps: *const *const u32,
+                                      heights: *const usize, n_chips: usize, on_device: c_int,
+                                      mult_out: *mut u32,
+                                      report: *mut bfz_lookups_mult_report) -> c_int;
 
     pub fn bfz_lookups_time(prog: *const u8, len: usize, chip: c_int, main: *const u32,
                             prep: *const u32, height: usize, alpha: *const u32, beta: *const u32,

@@ -808,6 +808,66 @@ int bfz_lookups_time(const uint8_t* prog, size_t len, int chip, const uint32_t* 
                      const uint32_t* prep, size_t height, const uint32_t alpha[4],
                      const uint32_t beta[4], int runs, float* prog_ms, float* chip_ms);
 
+/* ---- Per-key lookup discrepancies and multiplicity columns for caller-defined chips: what
+ * bfz_debug_interactions_traces reports for the built-in chips (debug_interactions_with_all_chips,
+ * crates/stark/src/lookup/debug.rs:59-196), for chips given as interaction programs, and the
+ * column a table chip needs before any trace of it exists.  Conventions of bfz_lookups_balance:
+ * row-major Montgomery words, heights a power of two in [1, 2^23], words >= p refused with the
+ * same message, preps may be NULL.  A chip's index is its position in the caller's arrays; at most
+ * BFZ_LOOKUPS_DEBUG_MAX_CHIPS chips.  A kind >= 2^24 is refused (a key's first word is
+ * kind << 8 | n_values); the message names the chip and the interaction.  on_device = 0 is a
+ * single-threaded host path over the same compiled lists (no device needed).
+ *
+ *   bfz_lookups_debug            kinds: n_kinds canonical kind values, NULL / 0 selects all.  out
+ *                                receives the first min(unbalanced_keys, cap) records in ascending
+ *                                order of (kind, then the values' canonical integers); chip_net and
+ *                                chip_count receive cap x n_chips words, record r's share of chip c
+ *                                at [r * n_chips + c] (cap > 0 needs all three).
+ *                                report->chip_distinct is the caller's array of n_chips words.
+ *                                first_interaction is the index in the program's chain order,
+ *                                whatever kinds selects.  Returns 0 whenever the check ran.
+ *   bfz_lookups_multiplicities   the multiplicity column of a table chip: every interaction of the
+ *                                n_chips sender chips is aggregated (sends positive, receives
+ *                                negative); mult_out[row] is the net, mod p, of the key that
+ *                                interaction `interaction` of the table program (normally its
+ *                                receive) has on that row.  Rows that hold the same key: the first
+ *                                gets everything, the others 0.  The table's own multiplicity
+ *                                expression is not read.  unmatched counts the sent keys no table
+ *                                row holds; first is the smallest of them with the senders' witness
+ *                                (chip_* unused). */
+#define BFZ_LOOKUPS_DEBUG_MAX_CHIPS 32
+typedef struct {
+  int32_t kind, nvals;
+  uint32_t values[BFZ_LOOKUP_MAX_VALUES]; /* Montgomery; unused entries 0 */
+  int32_t net;                            /* field_to_int(sends - receives) over all chips */
+  int32_t first_chip, first_interaction;  /* witness: the smallest (chip, row, interaction) */
+  int64_t first_row;                      /* natural row order */
+} bfz_lookups_discrepancy;
+typedef struct {
+  int32_t balanced, total_net;
+  uint64_t interactions, distinct_keys, unbalanced_keys;
+  uint64_t* chip_distinct;         /* caller's array of n_chips words */
+  uint32_t n_written;              /* min(unbalanced_keys, cap) */
+  uint32_t rounds, tag_collisions; /* diagnostics of the device path, 0 on the host path */
+  uint32_t _pad;
+  uint64_t table_bytes;
+} bfz_lookups_report;
+typedef struct {
+  uint64_t interactions, distinct_keys, unmatched;
+  bfz_lookups_discrepancy first;   /* valid when unmatched > 0 */
+} bfz_lookups_mult_report;
+int bfz_lookups_debug(const uint8_t* const* progs, const size_t* lens, const uint32_t* const* mains,
+                      const uint32_t* const* preps, const size_t* heights, size_t n_chips,
+                      const uint32_t* kinds, size_t n_kinds, int on_device,
+                      bfz_lookups_report* report, bfz_lookups_discrepancy* out, int32_t* chip_net,
+                      uint32_t* chip_count, size_t cap);
+int bfz_lookups_multiplicities(const uint8_t* table_prog, size_t table_len,
+                               const uint32_t* table_main, const uint32_t* table_prep,
+                               size_t table_height, int interaction, const uint8_t* const* progs,
+                               const size_t* lens, const uint32_t* const* mains,
+                               const uint32_t* const* preps, const size_t* heights, size_t n_chips,
+                               int on_device, uint32_t* mult_out, bfz_lookups_mult_report* report);
+
 /* ---- Caller-defined chips of a machine: an AIR program (BFA1, optional) paired with an
  * interaction program (BFL1).  Chip::eval (crates/stark/src/chip.rs:222-228) evaluates the AIR and
  * then the permutation constraints (crates/stark/src/permutation.rs:157-272); here both halves are
@@ -879,7 +939,8 @@ int bfz_set_pcs_variant(int observe_openings);
  * bfz_uni_verify_batch with on_device = 1 run their host side only (stages, packing, the queries
  * the packing keeps on the host) with a stand-in for the kernels that reports no failure and needs
  * no device, so that side is testable without a GPU (tests/test_verify_batch.py,
- * tests/test_uni_device.py); its verdicts are then not a verification.  Bit 2 cuts the key hash of the device path of bfz_*_debug_interactions to its low
+ * tests/test_uni_device.py); its verdicts are then not a verification.  Bit 2 cuts the key hash of the device path of bfz_*_debug_interactions, bfz_lookups_debug and
+ * bfz_lookups_multiplicities to its low
  * 12 bits before anything uses it (home slot and tag alike), so distinct keys share tags and the
  * multi-round path runs; verdicts and records must not change.  0 (default) = off. */
 int bfz_set_fault_injection(int mask);

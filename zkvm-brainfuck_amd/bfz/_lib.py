@@ -90,6 +90,28 @@ class LookupReportC(ctypes.Structure):
                 ("rounds", c_uint32), ("tag_collisions", c_uint32), ("table_bytes", c_uint64)]
 
 
+class LookupsDiscrepancyC(ctypes.Structure):
+    """bfz_lookups_discrepancy: a key of caller-defined chips; the chips' shares are side arrays."""
+    _fields_ = [("kind", c_int32), ("nvals", c_int32), ("values", c_uint32 * LOOKUP_MAX_VALUES),
+                ("net", c_int32), ("first_chip", c_int32), ("first_interaction", c_int32),
+                ("first_row", c_int64)]
+
+
+class LookupsReportC(ctypes.Structure):
+    """bfz_lookups_report: bfz_lookup_report with chip_distinct as the caller's array."""
+    _fields_ = [("balanced", c_int32), ("total_net", c_int32), ("interactions", c_uint64),
+                ("distinct_keys", c_uint64), ("unbalanced_keys", c_uint64),
+                ("chip_distinct", POINTER(c_uint64)), ("n_written", c_uint32),
+                ("rounds", c_uint32), ("tag_collisions", c_uint32), ("_pad", c_uint32),
+                ("table_bytes", c_uint64)]
+
+
+class LookupsMultReportC(ctypes.Structure):
+    """bfz_lookups_mult_report: the outcome of bfz_lookups_multiplicities."""
+    _fields_ = [("interactions", c_uint64), ("distinct_keys", c_uint64), ("unmatched", c_uint64),
+                ("first", LookupsDiscrepancyC)]
+
+
 class UniCheckC(ctypes.Structure):
     """bfz_uni_check_result: the AIR-only row check of one chip."""
     _fields_ = [("chip", c_int32), ("num_constraints", c_int32), ("height", c_uint64),
@@ -269,6 +291,17 @@ SIGNATURES = [
     ("bfz_lookups_time", c_int, [POINTER(c_uint8), c_size_t, c_int, POINTER(c_uint32),
                                  POINTER(c_uint32), c_size_t, POINTER(c_uint32), POINTER(c_uint32),
                                  c_int, POINTER(ctypes.c_float), POINTER(ctypes.c_float)]),
+    ("bfz_lookups_debug", c_int, [POINTER(POINTER(c_uint8)), POINTER(c_size_t),
+                                  POINTER(POINTER(c_uint32)), POINTER(POINTER(c_uint32)),
+                                  POINTER(c_size_t), c_size_t, POINTER(c_uint32), c_size_t, c_int,
+                                  POINTER(LookupsReportC), POINTER(LookupsDiscrepancyC),
+                                  POINTER(c_int32), POINTER(c_uint32), c_size_t]),
+    ("bfz_lookups_multiplicities", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint32),
+                                           POINTER(c_uint32), c_size_t, c_int,
+                                           POINTER(POINTER(c_uint8)), POINTER(c_size_t),
+                                           POINTER(POINTER(c_uint32)), POINTER(POINTER(c_uint32)),
+                                           POINTER(c_size_t), c_size_t, c_int, POINTER(c_uint32),
+                                           POINTER(LookupsMultReportC)]),
     ("bfz_chip_info", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint8), c_size_t,
                               POINTER(ChipShapeC)]),
     ("bfz_chip_check_rows", c_int, [POINTER(c_uint8), c_size_t, POINTER(c_uint8), c_size_t,

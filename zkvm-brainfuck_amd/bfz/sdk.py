@@ -1485,6 +1485,90 @@ def lookups_balance(progs, mains, preps, alpha, beta, on_device: bool = True) ->
     return LookupsBalance(bool(ok.value), list(total), [list(cums[4 * i:4 * i + 4]) for i in range(k)])
 
 
+def _lookups_chips_c(progs, mains, preps, what):
+    """The C arrays of a set of caller-defined chips (kept alive by the returned tuple)."""
+    k = len(progs)
+    u32p, u8p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint8)
+    chips = [_lookups_chip_args(lookups_info(p), m, pr, what) for p, m, pr in zip(progs, mains, preps)]
+    bufs = [u8buf(p) for p in progs]
+    return ((u8p * k)(*[ctypes.cast(b, u8p) for b, _ in bufs]),
+            (ctypes.c_size_t * k)(*[n for _, n in bufs]),
+            (u32p * k)(*[m.ctypes.data_as(u32p) for m, _ in chips]),
+            (u32p * k)(*[pr.ctypes.data_as(u32p) if pr is not None else u32p() for _, pr in chips]),
+            (ctypes.c_size_t * k)(*[m.shape[0] for m, _ in chips]), k, chips, bufs)
+
+
+def _lookups_record(r, chip_net=(), chip_count=()) -> LookupDiscrepancy:
+    return LookupDiscrepancy(
+        kind=r.kind, values=[r.values[v] * _RINV % _P for v in range(r.nvals)], net=r.net,
+        chip_net=list(chip_net), chip_count=list(chip_count), first_chip=r.first_chip,
+        first_row=r.first_row, first_interaction=r.first_interaction)
+
+
+def lookups_debug(progs, mains, preps, kinds=None, limit: int = 256,
+                  on_device: bool = True) -> LookupReport:
+    """bfz_lookups_debug: debug_interactions_with_all_chips (lookup/debug.rs:59-196) for
+    caller-defined chips.  progs, mains, preps as lookups_balance takes them; kinds: canonical kind
+    values (None = all).  A chip's index (first_chip, chip_net, chip_count, chip_distinct) is its
+    position in progs; first_interaction is the index in the program's chain order."""
+    if on_device:
+        init()
+    cprogs, clens, cmains, cpreps, cheights, k, *_keep = _lookups_chips_c(progs, mains, preps, "lookups_debug")
+    kinds = [int(x) for x in kinds] if kinds is not None else []
+    ckinds = (ctypes.c_uint32 * max(1, len(kinds)))(*kinds)
+    cap = int(limit)
+    distinct = (ctypes.c_uint64 * k)()
+    rep = _lib.LookupsReportC(chip_distinct=distinct)
+    recs = (_lib.LookupsDiscrepancyC * max(1, cap))()
+    nets, counts = (ctypes.c_int32 * max(1, cap * k))(), (ctypes.c_uint32 * max(1, cap * k))()
+    check(lib().bfz_lookups_debug(cprogs, clens, cmains, cpreps, cheights, k, ckinds, len(kinds),
+                                  int(bool(on_device)), ctypes.byref(rep), recs, nets, counts, cap))
+    ds = [_lookups_record(recs[i], nets[i * k:(i + 1) * k], counts[i * k:(i + 1) * k])
+          for i in range(rep.n_written)]
+    return LookupReport(
+        balanced=bool(rep.balanced), total_net=rep.total_net, interactions=rep.interactions,
+        distinct_keys=rep.distinct_keys, unbalanced_keys=rep.unbalanced_keys,
+        chip_distinct=list(distinct), discrepancies=ds, rounds=rep.rounds,
+        tag_collisions=rep.tag_collisions, table_bytes=rep.table_bytes)
+
+
+@dataclass
+class LookupsMultiplicities:
+    """bfz_lookups_multiplicities: mult holds one Montgomery word per table row; unmatched counts
+    the sent keys that no table row holds and first_unmatched is the smallest of them, with the
+    senders' witness (None when every key is in the table)."""
+    mult: "object"
+    interactions: int
+    distinct_keys: int
+    unmatched: int
+    first_unmatched: Optional[LookupDiscrepancy]
+
+
+def lookups_multiplicities(table_prog, table_main, table_prep, interaction: int, progs, mains, preps,
+                           on_device: bool = True) -> LookupsMultiplicities:
+    """bfz_lookups_multiplicities: the multiplicity column of a table chip from the chips that send
+    to it.  interaction: the table program's interaction whose key a row holds (normally its
+    receive); its own multiplicity expression is not read.  Rows that hold the same key: the first
+    gets everything."""
+    import numpy as np
+    if on_device:
+        init()
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    tmain, tprep = _lookups_chip_args(lookups_info(table_prog), table_main, table_prep,
+                                      "lookups_multiplicities")
+    cprogs, clens, cmains, cpreps, cheights, k, *_keep = _lookups_chips_c(
+        progs, mains, preps, "lookups_multiplicities")
+    tbuf, tn = u8buf(table_prog)
+    mult = np.zeros(tmain.shape[0], dtype=np.uint32)
+    rep = _lib.LookupsMultReportC()
+    check(lib().bfz_lookups_multiplicities(
+        tbuf, tn, tmain.ctypes.data_as(u32p), tprep.ctypes.data_as(u32p) if tprep is not None else None,
+        tmain.shape[0], int(interaction), cprogs, clens, cmains, cpreps, cheights, k,
+        int(bool(on_device)), mult.ctypes.data_as(u32p), ctypes.byref(rep)))
+    return LookupsMultiplicities(mult, rep.interactions, rep.distinct_keys, rep.unmatched,
+                                 _lookups_record(rep.first) if rep.unmatched else None)
+
+
 # ---- caller-defined chips of a machine: an AIR program paired with an interaction program
 @dataclass
 class ChipInfo:

@@ -1663,6 +1663,101 @@ int bfz_lookups_time(const uint8_t* prog, size_t len, int chip, const uint32_t* 
   });
 }
 
+}  // extern "C"
+namespace {
+// The chips of a bfz_lookups_debug / bfz_lookups_multiplicities call: ps owns the compiled programs.
+std::vector<bfz::LookupProgChip> lookup_prog_chips(const uint8_t* const* progs, const size_t* lens,
+                                                   const uint32_t* const* mains,
+                                                   const uint32_t* const* preps, const size_t* heights,
+                                                   size_t n_chips, const char* what,
+                                                   std::vector<bfz::LookupProgram>& ps) {
+  if (!progs || !lens || !mains || !heights) throw std::runtime_error("null argument");
+  if (n_chips < 1 || n_chips > BFZ_LOOKUPS_DEBUG_MAX_CHIPS)
+    throw std::runtime_error(std::string(what) + ": chip count not in [1, " +
+                             std::to_string(BFZ_LOOKUPS_DEBUG_MAX_CHIPS) + "]");
+  ps.reserve(n_chips);
+  std::vector<bfz::LookupProgChip> chips;
+  for (size_t i = 0; i < n_chips; i++) {
+    if (!progs[i]) throw std::runtime_error("null argument");
+    ps.push_back(bfz::lookups_compile(progs[i], lens[i]));
+    chips.push_back({&ps[i], mains[i], preps ? preps[i] : nullptr, heights[i]});
+  }
+  return chips;
+}
+void to_c(const bfz::LookupDiscrepancy& d, bfz_lookups_discrepancy& q) {
+  static_assert(sizeof(bfz_lookups_discrepancy) == 56 && sizeof(bfz_lookups_report) == 64 &&
+                    sizeof(bfz_lookups_mult_report) == 80, "bfz_lookups_* layouts");
+  static_assert(BFZ_LOOKUPS_DEBUG_MAX_CHIPS == bfz::LKD_MAX_CHIPS, "bfz.h sizes");
+  std::memset(&q, 0, sizeof q);
+  q.kind = d.kind;
+  q.nvals = d.nvals;
+  for (int v = 0; v < d.nvals; v++) q.values[v] = kb::to_mont(d.values[v]);
+  q.net = d.net;
+  q.first_chip = d.first_chip;
+  q.first_interaction = d.first_interaction;
+  q.first_row = d.first_row;
+}
+}  // namespace
+extern "C" {
+
+int bfz_lookups_debug(const uint8_t* const* progs, const size_t* lens, const uint32_t* const* mains,
+                      const uint32_t* const* preps, const size_t* heights, size_t n_chips,
+                      const uint32_t* kinds, size_t n_kinds, int on_device,
+                      bfz_lookups_report* report, bfz_lookups_discrepancy* out, int32_t* chip_net,
+                      uint32_t* chip_count, size_t cap) {
+  return guarded([&] {
+    if (!report || !report->chip_distinct || (n_kinds && !kinds)) throw std::runtime_error("null argument");
+    if (cap > 0 && (!out || !chip_net || !chip_count))
+      throw std::runtime_error("lookups_debug: cap > 0 needs the output arrays");
+    if (cap > 0xFFFFFFF0u) throw std::runtime_error("lookups_debug: cap too large");
+    std::vector<bfz::LookupProgram> ps;
+    const auto chips = lookup_prog_chips(progs, lens, mains, preps, heights, n_chips, "lookups_debug", ps);
+    bfz::LookupProgReport r;
+    bfz::lookups_debug(chips, kinds, n_kinds, on_device != 0, cap, (g_fault & 4) != 0, r);
+    uint64_t* distinct = report->chip_distinct;
+    std::memset(report, 0, sizeof *report);
+    report->chip_distinct = distinct;
+    report->balanced = r.rep.balanced;
+    report->total_net = r.rep.total_net;
+    report->interactions = r.rep.interactions;
+    report->distinct_keys = r.rep.distinct_keys;
+    report->unbalanced_keys = r.rep.unbalanced_keys;
+    std::copy(r.chip_distinct.begin(), r.chip_distinct.end(), distinct);
+    report->n_written = (uint32_t)r.rep.recs.size();
+    report->rounds = r.rep.rounds;
+    report->tag_collisions = r.rep.tag_collisions;
+    report->table_bytes = r.rep.table_bytes;
+    for (size_t k = 0; k < r.rep.recs.size(); k++) to_c(r.rep.recs[k], out[k]);
+    std::copy(r.chip_net.begin(), r.chip_net.end(), chip_net);
+    std::copy(r.chip_count.begin(), r.chip_count.end(), chip_count);
+    return 0;
+  });
+}
+
+int bfz_lookups_multiplicities(const uint8_t* table_prog, size_t table_len,
+                               const uint32_t* table_main, const uint32_t* table_prep,
+                               size_t table_height, int interaction, const uint8_t* const* progs,
+                               const size_t* lens, const uint32_t* const* mains,
+                               const uint32_t* const* preps, const size_t* heights, size_t n_chips,
+                               int on_device, uint32_t* mult_out, bfz_lookups_mult_report* report) {
+  return guarded([&] {
+    if (!table_prog || !mult_out || !report) throw std::runtime_error("null argument");
+    std::vector<bfz::LookupProgram> ps;
+    const auto chips =
+        lookup_prog_chips(progs, lens, mains, preps, heights, n_chips, "lookups_multiplicities", ps);
+    const bfz::LookupProgram tp = bfz::lookups_compile(table_prog, table_len);
+    bfz::LookupMultReport r;
+    bfz::lookups_multiplicities({&tp, table_main, table_prep, table_height}, interaction, chips,
+                                on_device != 0, (g_fault & 4) != 0, mult_out, r);
+    std::memset(report, 0, sizeof *report);
+    report->interactions = r.interactions;
+    report->distinct_keys = r.distinct_keys;
+    report->unmatched = r.unmatched;
+    to_c(r.first, report->first);
+    return 0;
+  });
+}
+
 // ---- caller-defined chips of a machine: an AIR program paired with an interaction program
 // (chip_program.h)
 }  // extern "C"

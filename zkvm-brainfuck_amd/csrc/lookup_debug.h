@@ -85,4 +85,44 @@ void debug_interactions_host(const Program& program, const int* chips,
 void debug_interactions_device(const ProvingKey& pk, const DeviceTraces& dt, unsigned kinds_mask,
                                size_t cap, bool low_hash_bits, LookupReport& out);
 
+// ---- The same for caller-defined chips, each given as a compiled interaction program
+// (lookup_program.h) with row-major natural-order host traces in Montgomery words
+// (lookup_debug_prog.hip).  A chip's index is its position in the caller's array; at most 32, the
+// width of a slot's chip mask.  first_interaction is the index in the program's chain order,
+// whatever the kind selection.
+struct LookupProgram;
+constexpr int LKD_MAX_CHIPS = 32;
+
+struct LookupProgChip {
+  const LookupProgram* prog;
+  const uint32_t* main;
+  const uint32_t* prep;  // nullptr when the program has no preprocessed columns
+  size_t height;
+};
+
+struct LookupProgReport {
+  LookupReport rep;                     // its fixed per-chip arrays stay 0
+  std::vector<uint64_t> chip_distinct;  // n_chips
+  std::vector<int32_t> chip_net;        // rep.recs.size() x n_chips
+  std::vector<uint32_t> chip_count;
+};
+
+struct LookupMultReport {
+  uint64_t interactions = 0, distinct_keys = 0, unmatched = 0;
+  LookupDiscrepancy first;  // the smallest unmatched key, its net and its witness (unmatched > 0)
+};
+
+// kinds: canonical kind values, n_kinds = 0 selects all.  Throws for more than 32 chips, a kind
+// >= 2^24 (the key's first word is kind << 8 | nvals), a bad height or a word >= p.
+// on_device = false: single-threaded over the same lists and a std::map, no device.
+void lookups_debug(const std::vector<LookupProgChip>& chips, const uint32_t* kinds, size_t n_kinds,
+                   bool on_device, size_t cap, bool low_hash_bits, LookupProgReport& out);
+
+// The multiplicity column of a table chip: mult_out[row] = the net of the senders' interactions
+// whose key is the key of the table's interaction `interaction` on that row (Montgomery word), for
+// the first row that holds the key, 0 for a later one; the table's own multiplicity is not read.
+void lookups_multiplicities(const LookupProgChip& table, int interaction,
+                            const std::vector<LookupProgChip>& senders, bool on_device,
+                            bool low_hash_bits, uint32_t* mult_out, LookupMultReport& out);
+
 }  // namespace bfz

@@ -29,7 +29,7 @@
 // it reads is already smaller.
 //
 // These kernels are not part of a proof and are NOT in a PreloadKernels list.
-#include "lookup_debug.h"
+#include "lookup_debug_dev.h"
 
 #include <algorithm>
 #include <cstring>
@@ -45,30 +45,6 @@ namespace {
 constexpr int LK_MAIN_W[NUM_CHIPS] = {31, 1, 7, 45, 12, 2, 41, 5};
 constexpr int LK_PREP_W[NUM_CHIPS] = {0, 6, 0, 0, 0, 2, 0, 0};
 constexpr unsigned LK_ALL_KINDS = 0xFEu;
-constexpr uint32_t LK_MAX_ROUNDS = 1u << 12;
-constexpr int LK_MAX_BLOCKS = 2048;
-constexpr int LK_CACHE_LOG = 11, LK_CACHE = 1 << LK_CACHE_LOG;  // per-block LDS table (account)
-constexpr uint32_t LK_NO_SLOT = 0xFFFFFFFFu;
-constexpr uint32_t LK_ERR_FULL = 1, LK_ERR_STATE = 2;
-
-enum { PH_COUNT = 0, PH_CLAIM = 1, PH_MATERIALISE = 2, PH_ACCOUNT = 3, PH_SHARES = 4 };
-
-struct LkTable {
-  unsigned long long* tag;
-  unsigned long long* net;  // two's complement of the signed sum
-  unsigned long long* rep;
-  uint32_t* mask;
-  uint32_t* aux;  // rounds: the round the key was written in; shares pass: selected index + 1
-  uint32_t* key;  // LK_KEY_WORDS per slot
-  int logsize;
-};
-
-struct LkCtl {
-  unsigned long long interactions, unresolved, collisions;
-  unsigned long long distinct, unbalanced, chip_distinct[NUM_CHIPS], total, cursor;
-  uint32_t error, pad;
-};
-
 using LkKey = std::array<uint32_t, LK_KEY_WORDS>;
 
 void check_tables() {
@@ -230,98 +206,6 @@ __device__ __forceinline__ void lk_for(F&& f) {
   }
 }
 
-__device__ __forceinline__ unsigned long long lk_hash(const uint32_t (&key)[LK_KEY_WORDS]) {
-  unsigned long long h = 0x9E3779B97F4A7C15ull;
-#pragma unroll
-  for (int i = 0; i < LK_KEY_WORDS; i++) {
-    h = (h ^ key[i]) * 0xFF51AFD7ED558CCDull;
-    h ^= h >> 32;
-  }
-  h ^= h >> 29;
-  h *= 0xC4CEB9FE1A85EC53ull;
-  h ^= h >> 32;
-  return h;
-}
-
-__device__ __forceinline__ bool lk_key_equal(const uint32_t* __restrict__ slot_key,
-                                             const uint32_t (&key)[LK_KEY_WORDS]) {
-  const uint4 a = *reinterpret_cast<const uint4*>(slot_key);
-  const uint4 b = *reinterpret_cast<const uint4*>(slot_key + 4);
-  return a.x == key[0] && a.y == key[1] && a.z == key[2] && a.w == key[3] && b.x == key[4] &&
-         b.y == key[5] && b.z == key[6] && b.w == key[7];
-}
-
-__device__ __forceinline__ unsigned long long lk_load(const unsigned long long* p) {
-  // device-scope load: another CU's atomic on this word is seen, not an older L1 line
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The slot of round `round` for (key, tag), probing from `home`: the first slot of this tag whose
-// key is not written yet or was written in this round (resolved = false), or whose key, written
-// in an earlier round, is this key (resolved = true).  CLAIM: an empty slot is claimed.  -1 and
-// an error bit if the probe runs round the table, or (not CLAIM) meets an empty slot.
-template <bool CLAIM>
-__device__ __forceinline__ int lk_walk(const LkTable& T, const uint32_t (&key)[LK_KEY_WORDS],
-                                       unsigned long long tag, uint32_t home, uint32_t round,
-                                       bool& resolved, uint32_t& err) {
-  const uint32_t size = 1u << T.logsize, wrap = size - 1;
-  resolved = false;
-  for (uint32_t step = 0; step < size; step++) {
-    const uint32_t i = (home + step) & wrap;
-    unsigned long long t = CLAIM ? lk_load(&T.tag[i]) : T.tag[i];
-    if (t == 0) {
-      if (!CLAIM) {
-        err |= LK_ERR_STATE;
-        return -1;
-      }
-      t = atomicCAS(&T.tag[i], 0ull, tag);
-      if (t == 0) t = tag;
-    }
-    if (t != tag) continue;
-    const uint32_t rd = T.aux[i];
-    if (rd == 0 || rd == round) return (int)i;
-    if (lk_key_equal(T.key + (size_t)i * LK_KEY_WORDS, key)) {
-      resolved = true;
-      return (int)i;
-    }
-  }
-  err |= LK_ERR_FULL;
-  return -1;
-}
-
-// After the rounds: the slot that holds `key`, or -1 and an error bit.
-__device__ __forceinline__ int lk_find(const LkTable& T, const uint32_t (&key)[LK_KEY_WORDS],
-                                       unsigned long long tag, uint32_t home, uint32_t& err) {
-  const uint32_t size = 1u << T.logsize, wrap = size - 1;
-  for (uint32_t step = 0; step < size; step++) {
-    const uint32_t i = (home + step) & wrap;
-    const unsigned long long t = T.tag[i];
-    if (t == 0) break;
-    if (t == tag && lk_key_equal(T.key + (size_t)i * LK_KEY_WORDS, key)) return (int)i;
-  }
-  err |= LK_ERR_STATE;
-  return -1;
-}
-
-__device__ __forceinline__ unsigned long long lk_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// One atomicAdd per block (every thread of the block calls it).
-__device__ __forceinline__ void lk_block_add(unsigned long long v, unsigned long long* dst,
-                                             unsigned long long* sh4) {
-  v = lk_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long s = sh4[0] + sh4[1] + sh4[2] + sh4[3];
-    if (s) atomicAdd(dst, s);
-  }
-}
-
 template <int CHIP, int PHASE>
 __global__ __launch_bounds__(256) void k_lookup(const uint32_t* __restrict__ mainc,
                                                 const uint32_t* __restrict__ prepc, uint32_t n,
@@ -456,6 +340,34 @@ __global__ __launch_bounds__(256) void k_lookup_scan(LkTable T, LkCtl* __restric
   for (int c = 0; c < NUM_CHIPS; c++) lk_block_add(per_chip[c], &ctl->chip_distinct[c], sh4);
 }
 
+// k_lookup_scan for a run-time chip count (up to the 32 bits of the mask): the per-chip counters
+// are a block's LDS words, one LDS atomic per set bit of a slot's mask -- a register array
+// indexed by the bit would go to scratch -- and come out in chip_distinct[nchips], not in ctl.
+__global__ __launch_bounds__(256) void k_lookup_scan_n(LkTable T, LkCtl* __restrict__ ctl,
+                                                       unsigned long long* __restrict__ chip_distinct,
+                                                       uint32_t nchips) {
+  __shared__ unsigned long long sh4[4];
+  __shared__ unsigned long long per_chip[32];
+  if (threadIdx.x < 32) per_chip[threadIdx.x] = 0;
+  __syncthreads();
+  const size_t size = (size_t)1 << T.logsize;
+  unsigned long long distinct = 0, unbalanced = 0, total = 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < size;
+       i += (size_t)gridDim.x * blockDim.x) {
+    if (T.tag[i] == 0) continue;
+    distinct++;
+    for (uint32_t m = T.mask[i]; m; m &= m - 1) atomicAdd(&per_chip[__ffs(m) - 1], 1ull);
+    const long long net = (long long)T.net[i];
+    total += (unsigned long long)net;
+    if (net % (long long)P != 0) unbalanced++;
+  }
+  lk_block_add(distinct, &ctl->distinct, sh4);
+  lk_block_add(unbalanced, &ctl->unbalanced, sh4);
+  lk_block_add(total, &ctl->total, sh4);  // (its barriers order the LDS atomics above)
+  if (threadIdx.x < nchips && per_chip[threadIdx.x])
+    atomicAdd(&chip_distinct[threadIdx.x], per_chip[threadIdx.x]);
+}
+
 // The unbalanced slots as records of 14 words: slot, pad, net (2), representative (2), key (8).
 // A cursor hands out the positions; the host sorts.
 constexpr int LK_REC_WORDS = 14;
@@ -493,40 +405,24 @@ __global__ __launch_bounds__(256) void k_lookup_mark(LkTable T, const uint32_t* 
 namespace {
 template <int CHIP, int PHASE>
 void launch_phase(const uint32_t* mainc, const uint32_t* prepc, size_t h, unsigned kinds_mask,
-                  unsigned long long hash_mask, uint32_t round, const LkTable& T, LkCtl* ctl,
-                  unsigned long long* share_net, uint32_t* share_count, hipStream_t st) {
-  // BFZ_LOOKUP_COMBINE=0: every account goes to HBM, no per-block LDS table (A/B of DESIGN.md)
-  static const uint32_t combine = [] {
-    const char* e = std::getenv("BFZ_LOOKUP_COMBINE");
-    return (e && e[0] == '0' && !e[1]) ? 0u : 1u;
-  }();
+                  const LkPass& p) {
   const int nblocks = (int)std::min<size_t>(ceil_div(h, 256), LK_MAX_BLOCKS);
-  hipLaunchKernelGGL((k_lookup<CHIP, PHASE>), dim3(nblocks), dim3(256), 0, st, mainc, prepc,
-                     (uint32_t)h, log2i(h), kinds_mask, hash_mask, round, combine, T, ctl, share_net,
-                     share_count);
+  hipLaunchKernelGGL((k_lookup<CHIP, PHASE>), dim3(nblocks), dim3(256), 0, p.st, mainc, prepc,
+                     (uint32_t)h, log2i(h), kinds_mask, p.hash_mask, p.round, p.combine, p.T, p.ctl,
+                     p.share_net, p.share_count);
   KCHECK();
 }
 
-template <int PHASE>
-void launch_chip(int chip, const uint32_t* mainc, const uint32_t* prepc, size_t h,
-                 unsigned kinds_mask, unsigned long long hash_mask, uint32_t round, const LkTable& T,
-                 LkCtl* ctl, unsigned long long* share_net, uint32_t* share_count, hipStream_t st) {
-#define BFZ_LK_CASE(C)                                                                          \
-  case C:                                                                                       \
-    launch_phase<C, PHASE>(mainc, prepc, h, kinds_mask, hash_mask, round, T, ctl, share_net,    \
-                           share_count, st);                                                    \
-    break;
-  switch (chip) {
-    BFZ_LK_CASE(CHIP_CPU)
-    BFZ_LK_CASE(CHIP_PROGRAM)
-    BFZ_LK_CASE(CHIP_ADDSUB)
-    BFZ_LK_CASE(CHIP_JUMP)
-    BFZ_LK_CASE(CHIP_MEMORY)
-    BFZ_LK_CASE(CHIP_BYTE)
-    BFZ_LK_CASE(CHIP_MEMINSTRS)
-    BFZ_LK_CASE(CHIP_IO)
+template <int CHIP>
+void launch_chip(const uint32_t* mainc, const uint32_t* prepc, size_t h, unsigned kinds_mask,
+                 const LkPass& p) {
+  switch (p.phase) {
+    case PH_COUNT: launch_phase<CHIP, PH_COUNT>(mainc, prepc, h, kinds_mask, p); break;
+    case PH_CLAIM: launch_phase<CHIP, PH_CLAIM>(mainc, prepc, h, kinds_mask, p); break;
+    case PH_MATERIALISE: launch_phase<CHIP, PH_MATERIALISE>(mainc, prepc, h, kinds_mask, p); break;
+    case PH_ACCOUNT: launch_phase<CHIP, PH_ACCOUNT>(mainc, prepc, h, kinds_mask, p); break;
+    case PH_SHARES: launch_phase<CHIP, PH_SHARES>(mainc, prepc, h, kinds_mask, p); break;
   }
-#undef BFZ_LK_CASE
 }
 
 LkCtl fetch_ctl(const LkCtl* ctl_d, hipStream_t st) {
@@ -539,45 +435,32 @@ LkCtl fetch_ctl(const LkCtl* ctl_d, hipStream_t st) {
 }
 }  // namespace
 
-void debug_interactions_device(const ProvingKey& pk, const DeviceTraces& dt, unsigned kinds_mask,
-                               size_t cap, bool low_hash_bits, LookupReport& out) {
-  check_kinds_mask(kinds_mask);
-  check_tables();
+int32_t lk_net_to_int(long long net) { return net_to_int(net); }
+
+// The rounds driver (lookup_debug_dev.h).  out.recs get the key, the net and the witness; the
+// chips' shares and distinct-key counts go to sh, d.stride words per record.
+void lk_aggregate(const LkDriver& d, size_t cap, bool low_hash_bits, LookupReport& out, LkShares& sh) {
+  // BFZ_LOOKUP_COMBINE=0: every account goes to HBM, no per-block LDS table (A/B of DESIGN.md)
+  static const uint32_t combine = [] {
+    const char* e = std::getenv("BFZ_LOOKUP_COMBINE");
+    return (e && e[0] == '0' && !e[1]) ? 0u : 1u;
+  }();
   hipStream_t st = stream();
-  const int nc = (int)dt.chips.size();
-  if (nc == 0 || nc > NUM_CHIPS) throw std::runtime_error("debug_interactions: no traces");
-  std::vector<int> ord(nc);  // machine order (debug.rs:139-144); the result does not depend on it
-  std::iota(ord.begin(), ord.end(), 0);
-  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return dt.chips[a] < dt.chips[b]; });
-  std::vector<const uint32_t*> preps(nc, nullptr);
-  for (int k = 0; k < nc; k++) {
-    const int c = dt.chips[ord[k]];
-    const size_t h = dt.heights[ord[k]];
-    if (c < 0 || c >= NUM_CHIPS) throw std::runtime_error("debug_interactions: bad chip index");
-    if (h < 1 || (h & (h - 1)) || h > ((size_t)1 << 23))
-      throw std::runtime_error("debug_interactions: height not a power of two in [1, 2^23]");
-    const int pi = pk.idx_of_chip[c];
-    if (pi >= 0) {  // the key's preprocessed trace has the program's height (machine.rs:309-312)
-      if (pk.prep.mats[pi].n != h)
-        throw std::runtime_error(std::string("debug_constraints: height of ") + CHIP_INFO[c].name +
-                                 " differs from its preprocessed trace");
-      preps[k] = pk.prep_evals[pi].p;
-    }
-  }
-  const unsigned long long hash_mask = low_hash_bits ? 0xFFFull : ~0ull;
+  const size_t stride = (size_t)d.stride;
   out = LookupReport();
+  sh = LkShares();
+  sh.chip_distinct.assign(stride, 0);
 
   DBuf<LkCtl> ctl(1);
   HIP_CHECK(hipMemsetAsync(ctl.p, 0, sizeof(LkCtl), st));
-  LkTable T{};
-  auto each_chip = [&](auto phase, uint32_t round, unsigned long long* share_net, uint32_t* share_count) {
-    for (int k = 0; k < nc; k++)
-      launch_chip<decltype(phase)::value>(dt.chips[ord[k]], dt.evals[ord[k]].p, preps[k],
-                                          dt.heights[ord[k]], kinds_mask, hash_mask, round, T, ctl.p,
-                                          share_net, share_count, st);
+  LkPass pass{PH_COUNT, 0, low_hash_bits ? 0xFFFull : ~0ull, combine, LkTable{}, ctl.p, nullptr, nullptr, st};
+  auto each_chip = [&](int phase, uint32_t round) {
+    pass.phase = phase;
+    pass.round = round;
+    for (int k = 0; k < d.nchips; k++) d.launch(k, pass);
   };
   // the non-zero interactions: the report's count and the table's size
-  each_chip(std::integral_constant<int, PH_COUNT>{}, 0, nullptr, nullptr);
+  each_chip(PH_COUNT, 0);
   out.interactions = fetch_ctl(ctl.p, st).interactions;
   if (out.interactions == 0) {
     out.balanced = true;
@@ -585,6 +468,7 @@ void debug_interactions_device(const ProvingKey& pk, const DeviceTraces& dt, uns
   }
   if (out.interactions > ((uint64_t)1 << 30))
     throw std::runtime_error("debug_interactions: more than 2^30 interactions");
+  LkTable& T = pass.T;
   T.logsize = 10;
   while (((uint64_t)1 << T.logsize) < out.interactions + out.interactions / 4) T.logsize++;
   const size_t size = (size_t)1 << T.logsize;
@@ -616,9 +500,9 @@ void debug_interactions_device(const ProvingKey& pk, const DeviceTraces& dt, uns
       throw std::runtime_error("debug_interactions: keys still unresolved after " +
                                std::to_string(LK_MAX_ROUNDS) + " rounds");
     HIP_CHECK(hipMemsetAsync(&ctl.p->unresolved, 0, 8, st));
-    each_chip(std::integral_constant<int, PH_CLAIM>{}, round, nullptr, nullptr);
-    each_chip(std::integral_constant<int, PH_MATERIALISE>{}, round, nullptr, nullptr);
-    each_chip(std::integral_constant<int, PH_ACCOUNT>{}, round, nullptr, nullptr);
+    each_chip(PH_CLAIM, round);
+    each_chip(PH_MATERIALISE, round);
+    each_chip(PH_ACCOUNT, round);
     const LkCtl c = fetch_ctl(ctl.p, st);
     out.rounds = round;
     out.tag_collisions = (uint32_t)std::min<unsigned long long>(c.collisions, 0xFFFFFFFFull);
@@ -626,14 +510,27 @@ void debug_interactions_device(const ProvingKey& pk, const DeviceTraces& dt, uns
   }
 
   const int scan_blocks = (int)std::min<size_t>(ceil_div(size, 256), LK_MAX_BLOCKS);
-  hipLaunchKernelGGL(k_lookup_scan, dim3(scan_blocks), dim3(256), 0, st, T, ctl.p);
-  KCHECK();
+  DBuf<unsigned long long> distinct_d;
+  if (d.runtime_stride) {
+    distinct_d.reset(stride);
+    HIP_CHECK(hipMemsetAsync(distinct_d.p, 0, stride * 8, st));
+    hipLaunchKernelGGL(k_lookup_scan_n, dim3(scan_blocks), dim3(256), 0, st, T, ctl.p, distinct_d.p,
+                       (uint32_t)stride);
+    KCHECK();
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "chip_distinct words");
+    HIP_CHECK(hipMemcpyAsync(sh.chip_distinct.data(), distinct_d.p, stride * 8, hipMemcpyDeviceToHost, st));
+  } else {
+    hipLaunchKernelGGL(k_lookup_scan, dim3(scan_blocks), dim3(256), 0, st, T, ctl.p);
+    KCHECK();
+  }
   const LkCtl c = fetch_ctl(ctl.p, st);
   out.distinct_keys = c.distinct;
   out.unbalanced_keys = c.unbalanced;
-  for (int k = 0; k < NUM_CHIPS; k++) out.chip_distinct[k] = c.chip_distinct[k];
+  if (!d.runtime_stride)
+    for (int k = 0; k < NUM_CHIPS; k++) sh.chip_distinct[k] = c.chip_distinct[k];
   out.total_net = net_to_int((long long)c.total);
   out.balanced = c.unbalanced == 0;
+  if (d.after_rounds) d.after_rounds(pass);
   if (c.unbalanced == 0 || cap == 0) return;
 
   // every unbalanced key comes to the host, which orders them and keeps the first `cap`
@@ -659,39 +556,94 @@ void debug_interactions_device(const ProvingKey& pk, const DeviceTraces& dt, uns
   // the chips' shares of the kept keys: one more pass over the interactions
   std::vector<uint32_t> slots(nsel);
   for (size_t k = 0; k < nsel; k++) slots[k] = recs[idx[k] * LK_REC_WORDS];
-  DBuf<uint32_t> slots_d(nsel), share_count(nsel * NUM_CHIPS);
-  DBuf<unsigned long long> share_net(nsel * NUM_CHIPS);
+  DBuf<uint32_t> slots_d(nsel), share_count(nsel * stride);
+  DBuf<unsigned long long> share_net(nsel * stride);
   HIP_CHECK(hipMemcpyAsync(slots_d.p, slots.data(), nsel * 4, hipMemcpyHostToDevice, st));
   HIP_CHECK(hipMemsetAsync(T.aux, 0, size * 4, st));
-  HIP_CHECK(hipMemsetAsync(share_count.p, 0, nsel * NUM_CHIPS * 4, st));
-  HIP_CHECK(hipMemsetAsync(share_net.p, 0, nsel * NUM_CHIPS * 8, st));
+  HIP_CHECK(hipMemsetAsync(share_count.p, 0, nsel * stride * 4, st));
+  HIP_CHECK(hipMemsetAsync(share_net.p, 0, nsel * stride * 8, st));
   hipLaunchKernelGGL(k_lookup_mark, dim3(ceil_div(nsel, 256)), dim3(256), 0, st, T,
                      (const uint32_t*)slots_d.p, (uint32_t)nsel);
   KCHECK();
-  each_chip(std::integral_constant<int, PH_SHARES>{}, 0, share_net.p, share_count.p);
-  std::vector<unsigned long long> snet(nsel * NUM_CHIPS);
-  std::vector<uint32_t> scount(nsel * NUM_CHIPS);
+  pass.share_net = share_net.p;
+  pass.share_count = share_count.p;
+  each_chip(PH_SHARES, 0);
+  std::vector<unsigned long long> snet(nsel * stride);
+  sh.count.resize(nsel * stride);
   HIP_CHECK(hipMemcpyAsync(snet.data(), share_net.p, snet.size() * 8, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipMemcpyAsync(scount.data(), share_count.p, scount.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(sh.count.data(), share_count.p, sh.count.size() * 4, hipMemcpyDeviceToHost, st));
   (void)fetch_ctl(ctl.p, st);
+  sh.net.assign(snet.begin(), snet.end());
 
   out.recs.resize(nsel);
   for (size_t k = 0; k < nsel; k++) {
     const uint32_t* r = &recs[idx[k] * LK_REC_WORDS];
-    LookupDiscrepancy& d = out.recs[k];
+    LookupDiscrepancy& dr = out.recs[k];
     LkKey key;
     std::memcpy(key.data(), r + 6, 4 * LK_KEY_WORDS);
-    fill_record(key, d);
-    d.net = net_to_int((long long)((unsigned long long)r[2] | ((unsigned long long)r[3] << 32)));
+    fill_record(key, dr);
+    dr.net = net_to_int((long long)((unsigned long long)r[2] | ((unsigned long long)r[3] << 32)));
     const unsigned long long rep = (unsigned long long)r[4] | ((unsigned long long)r[5] << 32);
-    d.first_chip = (int)(rep >> 32);
-    d.first_row = (int64_t)((rep & 0xFFFFFFFFull) >> 4);
-    d.first_interaction = (int)(rep & 15);
-    for (int c = 0; c < NUM_CHIPS; c++) {
-      d.chip_net[c] = net_to_int((long long)snet[k * NUM_CHIPS + c]);
-      d.chip_count[c] = scount[k * NUM_CHIPS + c];
+    dr.first_chip = (int)(rep >> 32);
+    dr.first_row = (int64_t)((rep & 0xFFFFFFFFull) >> d.rep_bits);
+    dr.first_interaction = (int)(rep & ((1u << d.rep_bits) - 1));
+  }
+}
+
+void debug_interactions_device(const ProvingKey& pk, const DeviceTraces& dt, unsigned kinds_mask,
+                               size_t cap, bool low_hash_bits, LookupReport& out) {
+  check_kinds_mask(kinds_mask);
+  check_tables();
+  const int nc = (int)dt.chips.size();
+  if (nc == 0 || nc > NUM_CHIPS) throw std::runtime_error("debug_interactions: no traces");
+  std::vector<int> ord(nc);  // machine order (debug.rs:139-144); the result does not depend on it
+  std::iota(ord.begin(), ord.end(), 0);
+  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return dt.chips[a] < dt.chips[b]; });
+  std::vector<const uint32_t*> preps(nc, nullptr);
+  for (int k = 0; k < nc; k++) {
+    const int c = dt.chips[ord[k]];
+    const size_t h = dt.heights[ord[k]];
+    if (c < 0 || c >= NUM_CHIPS) throw std::runtime_error("debug_interactions: bad chip index");
+    if (h < 1 || (h & (h - 1)) || h > ((size_t)1 << 23))
+      throw std::runtime_error("debug_interactions: height not a power of two in [1, 2^23]");
+    const int pi = pk.idx_of_chip[c];
+    if (pi >= 0) {  // the key's preprocessed trace has the program's height (machine.rs:309-312)
+      if (pk.prep.mats[pi].n != h)
+        throw std::runtime_error(std::string("debug_constraints: height of ") + CHIP_INFO[c].name +
+                                 " differs from its preprocessed trace");
+      preps[k] = pk.prep_evals[pi].p;
     }
   }
+  LkDriver d;
+  d.nchips = nc;
+  d.stride = NUM_CHIPS;
+  d.runtime_stride = false;
+  d.rep_bits = 4;
+  d.launch = [&](int k, const LkPass& p) {
+    const uint32_t* mainc = dt.evals[ord[k]].p;
+    const size_t h = dt.heights[ord[k]];
+#define BFZ_LK_CASE(C) \
+  case C: launch_chip<C>(mainc, preps[k], h, kinds_mask, p); break;
+    switch (dt.chips[ord[k]]) {
+      BFZ_LK_CASE(CHIP_CPU)
+      BFZ_LK_CASE(CHIP_PROGRAM)
+      BFZ_LK_CASE(CHIP_ADDSUB)
+      BFZ_LK_CASE(CHIP_JUMP)
+      BFZ_LK_CASE(CHIP_MEMORY)
+      BFZ_LK_CASE(CHIP_BYTE)
+      BFZ_LK_CASE(CHIP_MEMINSTRS)
+      BFZ_LK_CASE(CHIP_IO)
+    }
+#undef BFZ_LK_CASE
+  };
+  LkShares sh;
+  lk_aggregate(d, cap, low_hash_bits, out, sh);
+  for (int k = 0; k < NUM_CHIPS; k++) out.chip_distinct[k] = sh.chip_distinct[k];
+  for (size_t r = 0; r < out.recs.size(); r++)
+    for (int c = 0; c < NUM_CHIPS; c++) {
+      out.recs[r].chip_net[c] = net_to_int(sh.net[r * NUM_CHIPS + c]);
+      out.recs[r].chip_count[c] = sh.count[r * NUM_CHIPS + c];
+    }
 }
 
 }  // namespace bfz
