@@ -21,6 +21,10 @@ pub struct bfz_main_data {
 pub struct bfz_cycle_upload {
     _opaque: [u8; 0],
 }
+#[repr(C)]
+pub struct bfz_machine {
+    _opaque: [u8; 0],
+}
 
 /// p3 `DuplexChallenger<KoalaBear, Poseidon2KoalaBear<16>, 16, 8>` as plain data.
 #[repr(C)]
@@ -598,6 +602,27 @@ extern "C" {
                                   height: usize, alpha: *const u32, beta: *const u32,
                                   quot_alpha: *const u32, runs: c_int, prog_ms: *mut f32,
                                   chip_ms: *mut f32) -> c_int;
+
+    /// Machines of caller-defined chips: `StarkMachine::verify` (crates/stark/src/machine.rs:258-284)
+    /// and `MachineProver::commit` / `open` (crates/stark/src/prover.rs:209-236, 242-553) over chips
+    /// given as pairs of programs.
+    pub fn bfz_machine_create(names: *const *const u8, name_lens: *const usize,
+                              airs: *const *const u8, air_lens: *const usize,
+                              lookups: *const *const u8, lookups_lens: *const usize,
+                              preps: *const *const u32, prep_heights: *const usize, n_chips: usize,
+                              with_traces: c_int, prep_root: *const u32,
+                              out: *mut *mut bfz_machine) -> c_int;
+    pub fn bfz_machine_free(m: *mut bfz_machine);
+    pub fn bfz_machine_prep_root(m: *const bfz_machine, root: *mut u32) -> c_int;
+    pub fn bfz_machine_observe(m: *const bfz_machine, ch: *mut bfz_challenger) -> c_int;
+    pub fn bfz_machine_prove(m: *const bfz_machine, chips: *const c_int, traces: *const *const u32,
+                             heights: *const usize, n: usize, ch: *mut bfz_challenger,
+                             proof: *mut *mut u8, proof_len: *mut usize) -> c_int;
+    pub fn bfz_machine_verify(m: *const bfz_machine, ch: *mut bfz_challenger, proof: *const u8,
+                              proof_len: usize, out: *mut bfz_verify_outcome) -> c_int;
+    pub fn bfz_machine_time(m: *const bfz_machine, chips: *const c_int, traces: *const *const u32,
+                            heights: *const usize, n: usize, runs: c_int, perm_ms: *mut f32,
+                            quot_ms: *mut f32) -> c_int;
 
     pub fn bfz_set_num_queries(num_queries: c_int) -> c_int;
     pub fn bfz_set_pcs_variant(observe_openings: c_int) -> c_int;

@@ -924,6 +924,67 @@ int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const u
                            size_t height, const uint32_t alpha[4], const uint32_t beta[4],
                            const uint32_t quot_alpha[4], int runs, float* prog_ms, float* chip_ms);
 
+/* ---- Machines of caller-defined chips: StarkMachine::prove / verify
+ * (crates/stark/src/machine.rs:258-284; MachineProver::commit and ::open,
+ * crates/stark/src/prover.rs:209-236 and 242-553; Verifier::verify_shard,
+ * crates/stark/src/verifier.rs:27-216) for up to BFZ_MACHINE_MAX_CHIPS chips that are data, each
+ * an AIR program (optional) paired with an interaction program as in the bfz_chip_ calls, with a
+ * name (bytes, unique: the sort key of the commits, as a chip's name is in the reference).
+ *
+ *   bfz_machine_create   arrays of n_chips entries; airs[i] NULL / air_lens[i] 0 for a lookup-only
+ *                        chip.  with_traces = 1: preps[i] (row-major Montgomery words,
+ *                        prep_heights[i] x prep_width) for every chip with preprocessed columns;
+ *                        they are committed on the device as bfz_setup commits Program and Byte and
+ *                        prep_root is not read.  with_traces = 0: a verifier-only machine from
+ *                        prep_root (NULL when no chip has preprocessed columns) and prep_heights;
+ *                        no device is touched and bfz_machine_prove refuses.  Refusals name what is
+ *                        wrong: either program's own message, a duplicate name, too many chips, a
+ *                        preprocessed height that is not a power of two in [1, 2^23].
+ *   bfz_machine_prep_root  the preprocessed commitment (eight zero words without one).
+ *   bfz_machine_observe  StarkVerifyingKey::observe_into (crates/stark/src/prover.rs:595-601): the
+ *                        root, or eight zero words when no chip has preprocessed columns, then
+ *                        seven zeros.
+ *   bfz_machine_prove    chips[i] = index (in creation order) of the i-th included chip, traces[i]
+ *                        = its main trace, heights[i] a power of two in [1, 2^23]; words >= p are
+ *                        refused with bfz_uni_prove's message.  A chip with preprocessed columns
+ *                        must be included, at its preprocessed height.  At most 8 included chips
+ *                        may share one height (a commit hashes at most 16 matrices of one height
+ *                        and the quotient round has two per chip); more are refused before any
+ *                        device work with "machine: N chips of height H, a proof takes at most 8
+ *                        of one height".  bfz_machine_time has no such bound (it builds no
+ *                        trees).  ch is advanced as by
+ *                        bfz_open.  *proof (bfz_free): BFZ1 whose chip words are those indices; a
+ *                        machine without preprocessed columns has three input rounds per query.
+ *                        A trace that violates a constraint still proves; the verifier rejects.
+ *   bfz_machine_verify   host only; returns 0 whenever the check RAN, like bfz_uni_verify.  In
+ *                        order: shapes, the transcript, the sum of the cumulative sums
+ *                        ("cumulative sums do not sum to zero"; before the out-of-domain check, so
+ *                        that a changed sum is named as such), per chip the out-of-domain check
+ *                        ("OOD evaluation mismatch on chip NAME"), the PCS verification.
+ *   bfz_machine_time     diagnostic (scripts/machine_prove_time.py): HIP-event times, in ms, of
+ *                        the segmented launches (k_perm_rows_machine, k_quotient_machine: one
+ *                        launch over every chip) against the loop of per-chip launches
+ *                        (k_perm_rows_prog, k_quotient_chip_prog) on the same device inputs,
+ *                        alternating after one warm-up of each, whose words are compared.
+ *                        perm_ms / quot_ms: 2 * runs floats, the segmented form's then the loop's. */
+#define BFZ_MACHINE_MAX_CHIPS 32
+typedef struct bfz_machine bfz_machine;
+int bfz_machine_create(const uint8_t* const* names, const size_t* name_lens,
+                       const uint8_t* const* airs, const size_t* air_lens,
+                       const uint8_t* const* lookups, const size_t* lookups_lens,
+                       const uint32_t* const* preps, const size_t* prep_heights, size_t n_chips,
+                       int with_traces, const uint32_t prep_root[8], bfz_machine** out);
+void bfz_machine_free(bfz_machine* m);
+int bfz_machine_prep_root(const bfz_machine* m, uint32_t root[8]);
+int bfz_machine_observe(const bfz_machine* m, bfz_challenger* ch);
+int bfz_machine_prove(const bfz_machine* m, const int* chips, const uint32_t* const* traces,
+                      const size_t* heights, size_t n, bfz_challenger* ch, uint8_t** proof,
+                      size_t* proof_len);
+int bfz_machine_verify(const bfz_machine* m, bfz_challenger* ch, const uint8_t* proof,
+                       size_t proof_len, bfz_verify_outcome* out);
+int bfz_machine_time(const bfz_machine* m, const int* chips, const uint32_t* const* traces,
+                     const size_t* heights, size_t n, int runs, float* perm_ms, float* quot_ms);
+
 /* FRI_QUERIES (kb31_poseidon2.rs:59-62): 1..4096, or 0 = environment FRI_QUERIES / 84. */
 int bfz_set_num_queries(int num_queries);
 

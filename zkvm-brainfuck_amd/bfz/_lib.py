@@ -316,6 +316,22 @@ SIGNATURES = [
                                        POINTER(c_uint32), POINTER(c_uint32), c_size_t,
                                        POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
                                        c_int, POINTER(ctypes.c_float), POINTER(ctypes.c_float)]),
+    ("bfz_machine_create", c_int, [POINTER(POINTER(c_uint8)), POINTER(c_size_t),
+                                   POINTER(POINTER(c_uint8)), POINTER(c_size_t),
+                                   POINTER(POINTER(c_uint8)), POINTER(c_size_t),
+                                   POINTER(POINTER(c_uint32)), POINTER(c_size_t), c_size_t, c_int,
+                                   POINTER(c_uint32), POINTER(c_void_p)]),
+    ("bfz_machine_free", None, [c_void_p]),
+    ("bfz_machine_prep_root", c_int, [c_void_p, POINTER(c_uint32)]),
+    ("bfz_machine_observe", c_int, [c_void_p, POINTER(Challenger)]),
+    ("bfz_machine_prove", c_int, [c_void_p, POINTER(c_int), POINTER(POINTER(c_uint32)),
+                                  POINTER(c_size_t), c_size_t, POINTER(Challenger),
+                                  POINTER(POINTER(c_uint8)), POINTER(c_size_t)]),
+    ("bfz_machine_verify", c_int, [c_void_p, POINTER(Challenger), POINTER(c_uint8), c_size_t,
+                                   POINTER(VerifyOutcomeC)]),
+    ("bfz_machine_time", c_int, [c_void_p, POINTER(c_int), POINTER(POINTER(c_uint32)),
+                                 POINTER(c_size_t), c_size_t, c_int, POINTER(ctypes.c_float),
+                                 POINTER(ctypes.c_float)]),
     ("bfz_set_num_queries", c_int, [c_int]),
     ("bfz_set_pcs_variant", c_int, [c_int]),
     ("bfz_set_fault_injection", c_int, [c_int]),

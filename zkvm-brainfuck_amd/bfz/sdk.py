@@ -1681,6 +1681,133 @@ def chip_quotient_time(chip: int, air: Optional[bytes], lookups: bytes, main, pr
     return list(pm), list(cm)
 
 
+# ---- machines of caller-defined chips: StarkMachine::verify (crates/stark/src/machine.rs:258-284)
+# and MachineProver::commit / open (crates/stark/src/prover.rs:209-236, 242-553) over chip programs
+MACHINE_MAX_CHIPS = 32
+_CHECK_ALPHA, _CHECK_BETA = [_mont(5), _mont(7), _mont(11), _mont(13)], [_mont(2), _mont(3), 0, _mont(1)]
+
+
+class Machine:
+    """A machine whose chips are data (bfz_machine_*).  chips: [(name, air or None, lookups,
+    prep or None)], name str or bytes, prep the chip's preprocessed trace ((height, prep_width)
+    Montgomery words).  With every preprocessed trace given (or none needed) the traces are
+    committed on the device and the machine proves and verifies; with prep_root (8 Montgomery
+    words) and prep_heights ({name: height}) instead, it only verifies and touches no device.
+    Up to 32 chips; a proof takes at most 8 chips of one height (the Merkle commit hashes at most
+    16 matrices of one height and the quotient round has two per chip) and prove refuses more."""
+
+    def __init__(self, chips, prep_root=None, prep_heights=None):
+        import numpy as np
+        self.names = [n.encode() if isinstance(n, str) else bytes(n) for n, *_ in chips]
+        self.programs = [(air, lk) for _, air, lk, _ in chips]
+        verifier_only = prep_root is not None or prep_heights is not None
+        heights = {(k.encode() if isinstance(k, str) else bytes(k)): int(v)
+                   for k, v in (prep_heights or {}).items()}
+        k = len(chips)
+        u8p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+        keep = []
+
+        def bufs(items):
+            ptrs, lens = (u8p * k)(), (ctypes.c_size_t * k)()
+            for i, b in enumerate(items):
+                if b:
+                    buf, n = u8buf(b)
+                    keep.append(buf)
+                    ptrs[i], lens[i] = ctypes.cast(buf, u8p), n
+            return ptrs, lens
+
+        names, name_lens = bufs(self.names)
+        airs, air_lens = bufs([a for a, _ in self.programs])
+        lks, lk_lens = bufs([lk for _, lk in self.programs])
+        preps, hs = (u32p * k)(), (ctypes.c_size_t * k)()
+        self._check_preps = {}
+        for i, (_, _, _, prep) in enumerate(chips):
+            if prep is not None and not verifier_only:
+                t = np.ascontiguousarray(prep, dtype=np.uint32)
+                if t.ndim != 2:
+                    raise ValueError("Machine: a preprocessed trace must be a (height, width) matrix")
+                self._check_preps[i] = t
+                preps[i], hs[i] = t.ctypes.data_as(u32p), t.shape[0]
+            else:
+                hs[i] = heights.get(self.names[i], 0)
+        if not verifier_only:
+            init()
+        root = (ctypes.c_uint32 * 8)(*prep_root) if prep_root is not None else None
+        self._h = ctypes.c_void_p()
+        check(lib().bfz_machine_create(names, name_lens, airs, air_lens, lks, lk_lens, preps, hs, k,
+                                       0 if verifier_only else 1, root, ctypes.byref(self._h)))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib().bfz_machine_free(h)
+
+    @property
+    def prep_root(self) -> List[int]:
+        """The preprocessed commitment as 8 Montgomery words (zeros without preprocessed columns)."""
+        out = (ctypes.c_uint32 * 8)()
+        check(lib().bfz_machine_prep_root(self._h, out))
+        return list(out)
+
+    def observe(self, ch: Optional[Challenger] = None) -> Challenger:
+        """StarkVerifyingKey::observe_into on ch (fresh when None); returns it."""
+        if ch is None:
+            ch = Challenger()
+        check(lib().bfz_machine_observe(self._h, ctypes.byref(ch)))
+        return ch
+
+    def _traces_c(self, traces):
+        import numpy as np
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        items = [(self.names.index(n.encode() if isinstance(n, str) else bytes(n)),
+                  np.ascontiguousarray(t, dtype=np.uint32)) for n, t in traces.items()]
+        if any(t.ndim != 2 or t.shape[1] != chip_info(*self.programs[i]).main_width for i, t in items):
+            raise ValueError("Machine: a trace must be a (height, main_width) matrix of its chip")
+        k = len(items)
+        idx, ptrs, hs = (ctypes.c_int * k)(), (u32p * k)(), (ctypes.c_size_t * k)()
+        for j, (i, t) in enumerate(items):
+            idx[j], ptrs[j], hs[j] = i, t.ctypes.data_as(u32p), t.shape[0]
+        return idx, ptrs, hs, k, items
+
+    def prove(self, traces, ch: Challenger, check: bool = False) -> bytes:
+        """bfz_machine_prove: traces = {name: (height, main_width) Montgomery words} of the included
+        chips; ch (the state after observe) is advanced.  check=True runs chip_check on every chip
+        first, under fixed LogUp challenges, and raises BfzError naming the chip, row and constraint
+        of the first failing row; by default an invalid trace still proves."""
+        idx, ptrs, hs, k, items = self._traces_c(traces)
+        if check:
+            preps = self._check_preps
+            for i, t in items:
+                air, lk = self.programs[i]
+                prep = preps.get(i)
+                perm, cs = lookups_perm_trace(lk, t, prep, _CHECK_ALPHA, _CHECK_BETA)
+                res = chip_check(air, lk, t, prep, perm, _CHECK_ALPHA, _CHECK_BETA, cs)
+                if res.failing_rows:
+                    raise BfzError(f"Machine.prove: chip {self.names[i].decode(errors='replace')} "
+                                   f"violates its constraints: row {res.first_row}, constraint "
+                                   f"{res.first_constraint} ({res.failing_rows} failing rows)")
+        ptr, plen = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_size_t()
+        _lib.check(lib().bfz_machine_prove(self._h, idx, ptrs, hs, k, ctypes.byref(ch),
+                                           ctypes.byref(ptr), ctypes.byref(plen)))
+        return take_bytes(ptr, plen.value)
+
+    def verify(self, proof: bytes, ch: Challenger) -> VerifyOutcome:
+        """bfz_machine_verify (host only): the outcome, with the verifier's reason; ch advanced."""
+        buf, n = u8buf(proof)
+        out = _lib.VerifyOutcomeC()
+        check(lib().bfz_machine_verify(self._h, ctypes.byref(ch), buf, n, ctypes.byref(out)))
+        return VerifyOutcome(ok=bool(out.ok), query=out.query, why=out.why.decode())
+
+    def time(self, traces, runs: int = 20):
+        """bfz_machine_time (diagnostic): per-launch HIP-event milliseconds, as
+        {"perm": (segmented, loop), "quotient": (segmented, loop)}, `runs` each."""
+        idx, ptrs, hs, k, _ = self._traces_c(traces)
+        pm, qm = (ctypes.c_float * (2 * runs))(), (ctypes.c_float * (2 * runs))()
+        check(lib().bfz_machine_time(self._h, idx, ptrs, hs, k, int(runs), pm, qm))
+        return {"perm": (list(pm[:runs]), list(pm[runs:])),
+                "quotient": (list(qm[:runs]), list(qm[runs:]))}
+
+
 def set_num_queries(q: int) -> None:
     """FRI_QUERIES override (crates/stark/src/kb31_poseidon2.rs:59-62); 0 = environment/84."""
     check(lib().bfz_set_num_queries(int(q)))

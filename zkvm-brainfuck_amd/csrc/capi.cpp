@@ -21,6 +21,7 @@
 #include "logup.h"
 #include "lookup_debug.h"
 #include "lookup_program.h"
+#include "machine_program.h"
 #include "merkle.h"
 #include "ntt.h"
 #include "pcs_sharded.h"
@@ -40,6 +41,9 @@ struct bfz_pk {
 struct bfz_main_data {
   std::shared_ptr<const bfz::ProvingKey> pk;  // the key the commit was made for
   bfz::MainData md;
+};
+struct bfz_machine {
+  std::unique_ptr<bfz::MachineProgram> m;
 };
 struct bfz_record {
   bfz::DeviceEvents ev;  // executor events resident in HBM
@@ -2026,6 +2030,86 @@ int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const u
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
+    return 0;
+  });
+}
+
+// ---- machines of caller-defined chips (machine_program.h)
+int bfz_machine_create(const uint8_t* const* names, const size_t* name_lens,
+                       const uint8_t* const* airs, const size_t* air_lens,
+                       const uint8_t* const* lookups, const size_t* lookups_lens,
+                       const uint32_t* const* preps, const size_t* prep_heights, size_t n_chips,
+                       int with_traces, const uint32_t prep_root[8], bfz_machine** out) {
+  return guarded([&] {
+    if (!names || !name_lens || !airs || !air_lens || !lookups || !lookups_lens || !out)
+      throw std::runtime_error("null argument");
+    std::vector<bfz::MachineChipIn> in(n_chips);
+    for (size_t i = 0; i < n_chips; i++)
+      in[i] = bfz::MachineChipIn{names[i], name_lens[i], airs[i], lookups[i], air_lens[i],
+                                 lookups_lens[i], preps ? preps[i] : nullptr,
+                                 prep_heights ? prep_heights[i] : 0};
+    auto m = bfz::machine_create(in.data(), n_chips, with_traces != 0, prep_root);
+    *out = new bfz_machine{std::move(m)};
+    return 0;
+  });
+}
+
+void bfz_machine_free(bfz_machine* m) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  delete m;
+}
+
+int bfz_machine_prep_root(const bfz_machine* m, uint32_t root[8]) {
+  return guarded([&] {
+    if (!m || !root) throw std::runtime_error("null argument");
+    std::memcpy(root, m->m->prep_root, 32);
+    return 0;
+  });
+}
+
+int bfz_machine_observe(const bfz_machine* m, bfz_challenger* ch) {
+  return guarded([&] {
+    if (!m || !ch) throw std::runtime_error("null argument");
+    bfz::Challenger c = from_c(ch);
+    bfz::machine_observe(*m->m, c);
+    to_c(c, ch);
+    return 0;
+  });
+}
+
+int bfz_machine_prove(const bfz_machine* m, const int* chips, const uint32_t* const* traces,
+                      const size_t* heights, size_t n, bfz_challenger* ch, uint8_t** proof,
+                      size_t* len) {
+  return guarded([&] {
+    if (!m || !ch || !proof || !len) throw std::runtime_error("null argument");
+    bfz::Challenger c = from_c(ch);
+    auto v = bfz::machine_prove(*m->m, chips, traces, heights, n, c, opts());
+    const int r = emit(std::move(v), proof, len);
+    to_c(c, ch);  // advanced as by bfz_open
+    return r;
+  });
+}
+
+int bfz_machine_verify(const bfz_machine* m, bfz_challenger* ch, const uint8_t* proof, size_t len,
+                       bfz_verify_outcome* out) {
+  return guarded([&] {
+    if (!m || !ch || !out || (!proof && len)) throw std::runtime_error("null argument");
+    bfz::Challenger c = from_c(ch);
+    const bfz::ProveOptions o = opts();
+    bfz::VerifyOptions vo;
+    vo.num_queries = o.num_queries;
+    vo.observe_openings = o.observe_openings;
+    to_c(bfz::machine_verify(*m->m, c, proof, len, vo), out);
+    to_c(c, ch);
+    return 0;
+  });
+}
+
+int bfz_machine_time(const bfz_machine* m, const int* chips, const uint32_t* const* traces,
+                     const size_t* heights, size_t n, int runs, float* perm_ms, float* quot_ms) {
+  return guarded([&] {
+    if (!m) throw std::runtime_error("null argument");
+    bfz::machine_time(*m->m, chips, traces, heights, n, runs, perm_ms, quot_ms);
     return 0;
   });
 }

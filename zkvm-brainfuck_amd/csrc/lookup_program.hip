@@ -54,27 +54,6 @@ namespace bfz {
 
 using namespace kb;
 
-namespace {
-constexpr int LKP_T = 256;
-
-// The batch at list[at]: numerator and denominator of m_0 / d_0 + m_1 / d_1, or of m_0 / d_0.
-__device__ __forceinline__ void batch_frac(const RowCtx& c, int& at, bool pair, EF& num, EF& den) {
-  EF d0;
-  uint32_t m0;
-  interaction(c, at, d0, m0);
-  if (pair) {
-    EF d1;
-    uint32_t m1;
-    interaction(c, at, d1, m1);
-    num = ef_add(ef_mul_base(d1, m0), ef_mul_base(d0, m1));
-    den = ef_mul(d0, d1);
-  } else {
-    num = ef_base(m0);
-    den = d0;
-  }
-}
-}  // namespace
-
 // perm: 4 * (batches + 1) base columns of n rows (WRITE = 1; the last EF column is written by
 // perm_running_sum); rowsum[t]: the sum of row t's batch values.  Dynamic LDS: batches x 4 x
 // LKP_T words with WRITE = 1, none with WRITE = 0.  A zero denominator is not detected: its

@@ -53,5 +53,26 @@ __device__ __forceinline__ void interaction(const RowCtx& c, int& at, kb::EF& de
   const EF alpha{{c.chw[0], c.chw[1], c.chw[2], c.chw[3]}};
   den = ef_add(lz.get(), ef_add_base(alpha, kind));
 }
+
+constexpr int LKP_T = 256;  // threads per block of the permutation-row kernels
+
+// The batch at list[at]: numerator and denominator of m_0 / d_0 + m_1 / d_1, or of m_0 / d_0.
+__device__ __forceinline__ void batch_frac(const RowCtx& c, int& at, bool pair, kb::EF& num,
+                                           kb::EF& den) {
+  using namespace kb;
+  EF d0;
+  uint32_t m0;
+  interaction(c, at, d0, m0);
+  if (pair) {
+    EF d1;
+    uint32_t m1;
+    interaction(c, at, d1, m1);
+    num = ef_add(ef_mul_base(d1, m0), ef_mul_base(d0, m1));
+    den = ef_mul(d0, d1);
+  } else {
+    num = ef_base(m0);
+    den = d0;
+  }
+}
 }  // namespace
 }  // namespace bfz

@@ -1,0 +1,91 @@
+// A machine of caller-defined chips as a value, and its prover and verifier: what
+// StarkMachine::prove / verify (crates/stark/src/machine.rs:258-284, prover.rs:209-553,
+// verifier.rs:27-216) do for the eight compiled chips through ProvingKey, MainData and open_main,
+// done for up to 32 chip programs (chip_program.h).
+//   machine_create   the chips compiled and named; with preprocessed traces they are committed on
+//                    the device as setup commits them (one mixed-height MMCS, shift 1) -- without,
+//                    from a given root and heights, the machine only verifies.
+//   machine_observe  StarkVerifyingKey::observe_into (prover.rs:595-601).
+//   machine_prove    machine_program.hip: MachineProver::commit and ::open with the host
+//                    challenger; the two steps that interpret programs are one segmented launch
+//                    each over every chip (k_perm_rows_machine, k_quotient_machine).
+//   machine_verify   verifier.cpp: verify_shard for the machine.
+// A chip's main trace is opened at zeta alone exactly when it has an AIR that reads no next-row
+// value (AddSub, Jump and IO among the exported chips; a lookup-only chip is opened at both
+// points, as Program, Memory and Byte are).
+#pragma once
+#include <string>
+#include <vector>
+
+#include "chip_program.h"
+#include "prover.h"
+#include "verifier.h"
+
+namespace bfz {
+
+constexpr int MACHINE_MAX_CHIPS = BFZ_MACHINE_MAX_CHIPS;
+// Included chips of one height in a proof: a commit hashes at most 16 matrices of one height
+// (merkle.hip) and the quotient round has two chunks per chip.
+constexpr size_t MACHINE_MAX_SAME_HEIGHT = 8;
+
+struct MachineChip {
+  std::string name;  // bytes, unique in the machine
+  ChipProgram p;
+  bool local_only = false;
+  int prep_index = -1;   // its matrix in the preprocessed round, or -1
+  size_t prep_height = 0;
+  DBuf<uint32_t> code, list;     // the device lists (a proving machine)
+  DBuf<uint32_t> prep_evals;     // column-major bit-reversed preprocessed trace
+};
+
+struct MachineProgram {
+  std::vector<MachineChip> chips;
+  std::vector<int> prep_chips;  // chip of the k-th preprocessed matrix, sorted (Reverse(height), name)
+  bool has_prep = false, can_prove = false;
+  Round prep;                   // the committed preprocessed round (a proving machine)
+  uint32_t prep_root[8] = {0};
+  std::vector<std::string> names() const {
+    std::vector<std::string> v;
+    for (const MachineChip& c : chips) v.push_back(c.name);
+    return v;
+  }
+};
+
+struct MachineChipIn {
+  const uint8_t* name;
+  size_t name_len;
+  const uint8_t *air, *lookups;
+  size_t air_len, lookups_len;
+  const uint32_t* prep;  // row-major Montgomery words, or nullptr
+  size_t prep_height;    // of a chip with preprocessed columns
+};
+// with_traces: every chip with prep_width > 0 brings its trace (device work: the API lock is
+// held); otherwise root (8 Montgomery words, ignored when no chip has preprocessed columns) and
+// the heights describe the commitment and no device is touched.
+std::unique_ptr<MachineProgram> machine_create(const MachineChipIn* in, size_t n, bool with_traces,
+                                               const uint32_t* root);
+void machine_observe(const MachineProgram& m, Challenger& ch);
+
+// chips[i]: index in m.chips of the i-th included chip; traces[i]: row-major Montgomery words,
+// heights[i] x main width.  ch is advanced to the end of the opening.  Returns BFZ1 bytes whose
+// chip words are indices into m.chips.
+std::vector<uint8_t> machine_prove(const MachineProgram& m, const int* chips,
+                                   const uint32_t* const* traces, const size_t* heights, size_t n,
+                                   Challenger& ch, const ProveOptions& opt);
+VerifyOutcome machine_verify(const MachineProgram& m, Challenger& ch, const uint8_t* proof,
+                             size_t len, const VerifyOptions& opt);
+
+// Diagnostic (bfz_machine_time): single launches of the segmented kernels (form A) against the
+// loop of per-chip launches (form B) on the same device inputs, alternating after one warm-up of
+// each; perm_ms / quot_ms: [2][runs] HIP-event milliseconds (A then B).  Throws if the two forms'
+// words differ.
+void machine_time(const MachineProgram& m, const int* chips, const uint32_t* const* traces,
+                  const size_t* heights, size_t n, int runs, float* perm_ms, float* quot_ms);
+
+// The permutation constraints of a compiled interaction list over EF rows (the verifier at zeta),
+// in perm_constraints' order: batches + 3 values.  perm_l / perm_n: perm_width() EF columns.
+void chip_perm_eval_ef(const LookupProgram& lk, const EF* main_l, const EF* prep_l, const EF* perm_l,
+                       const EF* perm_n, const EF& alpha, const EF* beta_pows, const EF& cumsum,
+                       const EF& first, const EF& last, const EF& trans, EF* out);
+
+}  // namespace bfz

@@ -145,24 +145,10 @@ void read_opening_proof(In& r, ShardProof& pf) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------ BFZ1
-ShardProof decode_bfz1(const uint8_t* p, size_t n) {
-  In r{p, n};
-  ShardProof pf;
-  if (r.u32() != BFZ1_MAGIC) throw std::runtime_error("bad magic");
-  const uint32_t nc = r.u32();
-  if (nc == 0 || nc > NUM_CHIPS) throw std::runtime_error("bad chip count");
-  std::vector<bool> seen(NUM_CHIPS, false);
-  for (uint32_t i = 0; i < nc; i++) {
-    const uint32_t c = r.u32();
-    if (c >= (uint32_t)NUM_CHIPS || seen[c]) throw std::runtime_error("bad chip id");
-    seen[c] = true;
-    const size_t l = r.len(1);
-    r.need(l);
-    if (l != std::strlen(CHIP_INFO[c].name) || std::memcmp(p + r.off, CHIP_INFO[c].name, l) != 0)
-      throw std::runtime_error("chip name mismatch");
-    r.off += l;
-    pf.chips.push_back((int)c);
-  }
+namespace {
+// BFZ1 after the chip list: the roots, the opened values and the opening proof.
+ShardProof read_bfz1_body(In& r, ShardProof pf, size_t n) {
+  const uint32_t nc = (uint32_t)pf.chips.size();
   pf.main_root = r.digest();
   pf.perm_root = r.digest();
   pf.quot_root = r.digest();
@@ -185,6 +171,49 @@ ShardProof decode_bfz1(const uint8_t* p, size_t n) {
   read_opening_proof(r, pf);
   if (r.off != n) throw std::runtime_error("trailing bytes");
   return pf;
+}
+}  // namespace
+
+ShardProof decode_bfz1(const uint8_t* p, size_t n) {
+  In r{p, n};
+  ShardProof pf;
+  if (r.u32() != BFZ1_MAGIC) throw std::runtime_error("bad magic");
+  const uint32_t nc = r.u32();
+  if (nc == 0 || nc > NUM_CHIPS) throw std::runtime_error("bad chip count");
+  std::vector<bool> seen(NUM_CHIPS, false);
+  for (uint32_t i = 0; i < nc; i++) {
+    const uint32_t c = r.u32();
+    if (c >= (uint32_t)NUM_CHIPS || seen[c]) throw std::runtime_error("bad chip id");
+    seen[c] = true;
+    const size_t l = r.len(1);
+    r.need(l);
+    if (l != std::strlen(CHIP_INFO[c].name) || std::memcmp(p + r.off, CHIP_INFO[c].name, l) != 0)
+      throw std::runtime_error("chip name mismatch");
+    r.off += l;
+    pf.chips.push_back((int)c);
+  }
+  return read_bfz1_body(r, std::move(pf), n);
+}
+
+ShardProof decode_bfz1_machine(const uint8_t* p, size_t n, const std::vector<std::string>& names) {
+  In r{p, n};
+  ShardProof pf;
+  if (r.u32() != BFZ1_MAGIC) throw std::runtime_error("bad magic");
+  const uint32_t nc = r.u32();
+  if (nc == 0 || nc > names.size()) throw std::runtime_error("bad chip count");
+  std::vector<bool> seen(names.size(), false);
+  for (uint32_t i = 0; i < nc; i++) {
+    const uint32_t c = r.u32();
+    if (c >= names.size() || seen[c]) throw std::runtime_error("bad chip id");
+    seen[c] = true;
+    const size_t l = r.len(1);
+    r.need(l);
+    if (l != names[c].size() || std::memcmp(p + r.off, names[c].data(), l) != 0)
+      throw std::runtime_error("chip name mismatch");
+    r.off += l;
+    pf.chips.push_back((int)c);
+  }
+  return read_bfz1_body(r, std::move(pf), n);
 }
 
 // ------------------------------------------------------------------------------------ BFU1

@@ -12,6 +12,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "kb.h"
@@ -77,6 +78,12 @@ std::vector<uint8_t> encode_bfu1(const UniProof& u, uint32_t nq, const uint32_t*
                                  size_t nwords);
 
 ShardProof decode_bfz1(const uint8_t* p, size_t n);   // throws on malformed input
+// A proof of a machine of caller-defined chips (machine_program.h) is BFZ1 too: a chip word is the
+// chip's index in the machine's list (names[index] must follow it), up to names.size() chips.  A
+// machine without preprocessed columns commits no preprocessed round, so each of its queries
+// lists three input rounds (main, permutation, quotient); the count of input rounds is a length
+// word of the query encoding, so the four-round bytes are what they were.
+ShardProof decode_bfz1_machine(const uint8_t* p, size_t n, const std::vector<std::string>& names);
 std::vector<uint8_t> encode_bfz1(const ShardProof& pf);
 ShardProof decode_bincode(const uint8_t* p, size_t n, FieldRepr repr);
 std::vector<uint8_t> encode_bincode(const ShardProof& pf, FieldRepr repr);

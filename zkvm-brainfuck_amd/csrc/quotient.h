@@ -38,6 +38,9 @@ int num_constraints(int chip);
 // column 4k+e), rows in bit-reversed order of the chunk domain.
 // Builds (once per process) the selector-denominator table of the quotient domain 3 H_N, N = 2^logN.
 void prepare_quotient_tables(int logN);
+// The table itself (sel_inv[t], t a storage position of 3 H_N), for a launcher outside
+// quotient.hip (machine_program.hip); built on st at first use, as quotient_into builds it.
+const uint32_t* quotient_sel_inv(int logN, hipStream_t st);
 void quotient(int chip, const uint32_t* mainc, const uint32_t* prepc, const uint32_t* permc,
               int logN, const QuotParams& qp, uint32_t* qout, hipStream_t st);
 

@@ -141,6 +141,14 @@ void prepare_quotient_tables(int logN) {
   (void)sel_inv_table(logN, qp, stream());
 }
 
+const uint32_t* quotient_sel_inv(int logN, hipStream_t st) {
+  twiddles().ensure(logN);
+  QuotParams qp{};  // the fields k_sel_inv reads
+  qp.shift = to_mont(3);
+  qp.wn_inv = minv(two_adic_gen(logN - 1));
+  return sel_inv_table(logN, qp, st);
+}
+
 void quotient(int chip, const uint32_t* mainc, const uint32_t* prepc, const uint32_t* permc,
               int logN, const QuotParams& qp, uint32_t* qout, hipStream_t st) {
   const size_t N = (size_t)1 << logN;

@@ -16,6 +16,7 @@
 
 #include "air.h"
 #include "machine.h"
+#include "machine_program.h"
 #include "poseidon2.h"
 #include "prover.h"
 #include "quotient.h"
@@ -970,6 +971,150 @@ std::vector<VerifyOutcome> uni_verify_batch(const int* chips, Challenger* chs,
       },
       [](size_t, const UniState& U) { uni_after_queries(U); });
 }
+
+// ------------------------------------------------------------------ machines of chip programs
+// verify_shard (verifier.rs:27-216) for a machine of caller-defined chips (machine_program.h): the
+// shapes come from the machine's ChipPrograms, never from the proof; ch = the challenger after
+// machine_observe, advanced as far as the check got.
+VerifyOutcome machine_verify(const MachineProgram& m, Challenger& ch, const uint8_t* proof,
+                             size_t len, const VerifyOptions& opt) {
+  VerifyOutcome o;
+  try {
+    const ShardProof pf = decode_bfz1_machine(proof, len, m.names());
+    ShardState S;
+    S.pf = &pf;
+    const uint32_t nc = (uint32_t)pf.chips.size();
+    const std::vector<int>& chip = pf.chips;  // indices into m.chips, distinct (the decoder)
+    std::vector<ChipOpen>& co = S.co;
+    co.reserve(nc);
+    std::vector<int> at_of(m.chips.size(), -1);  // machine chip -> position in the proof
+    for (uint32_t i = 0; i < nc; i++) {
+      const ChipOpened& ov = pf.opened[i];
+      const MachineChip& mc = m.chips[chip[i]];
+      if (ov.log_degree > 23) throw std::runtime_error("log degree out of range");
+      co.push_back(ChipOpen{(int)ov.log_degree, ov.prep_local, ov.prep_next, ov.main_local,
+                            ov.main_next, ov.perm_local, ov.perm_next, ov.quotient, ov.cumsum});
+      const ChipOpen& c = co.back();
+      const size_t pw = (size_t)mc.p.lk.prep_w;
+      if (c.ml.size() != (size_t)mc.p.lk.main_w || c.mn.size() != c.ml.size() ||
+          c.perml.size() != 4 * (size_t)mc.p.perm_width() || c.permn.size() != c.perml.size() ||
+          c.pl.size() != pw || c.pn.size() != pw || c.q[0].size() != 4 || c.q[1].size() != 4)
+        throw std::runtime_error("opened-value shape mismatch");
+      if (mc.local_only)  // (as before_queries: the prover's zeros are required)
+        for (const std::vector<EF>* v : {&c.pn, &c.mn})
+          for (const EF& e : *v)
+            if (e.c[0] | e.c[1] | e.c[2] | e.c[3])
+              throw std::runtime_error("local-only chip with non-zero next values");
+      if (pw && ((size_t)1 << c.log_n) != mc.prep_height)
+        throw std::runtime_error("log degree is not the preprocessed height of chip " + mc.name);
+      at_of[chip[i]] = (int)i;
+    }
+    // ---- transcript (verifier.rs:76-101)
+    ch.observe_digest(pf.main_root.data());
+    S.pa = ch.sample_ef();
+    S.pb = ch.sample_ef();
+    ch.observe_digest(pf.perm_root.data());
+    for (uint32_t i = 0; i < nc; i++) ch.observe_ef(co[i].cumsum);
+    S.alpha = ch.sample_ef();
+    ch.observe_digest(pf.quot_root.data());
+    const EF zeta = S.zeta = ch.sample_ef();
+
+    // ---- rounds for the PCS verification: preprocessed (when the machine has one), main,
+    // permutation, quotient
+    int r = 0;
+    if (m.has_prep) {
+      for (int pc : m.prep_chips) {
+        if (at_of[pc] < 0) throw std::runtime_error("preprocessed chip missing from proof");
+        const MachineChip& mc = m.chips[pc];
+        const ChipOpen& c = co[at_of[pc]];
+        S.rounds[0].push_back(VMat{c.log_n, ONE, mc.p.lk.prep_w, mc.local_only ? 1 : 2,
+                                   {zeta, ef_mul_base(zeta, two_adic_gen(c.log_n))}, {&c.pl, &c.pn}});
+      }
+      S.roots[0] = m.prep_root;
+      r = 1;
+    }
+    for (uint32_t i = 0; i < nc; i++) {
+      const ChipOpen& c = co[i];
+      const EF znext = ef_mul_base(zeta, two_adic_gen(c.log_n));
+      S.rounds[r].push_back(VMat{c.log_n, ONE, (int)c.ml.size(), m.chips[chip[i]].local_only ? 1 : 2,
+                                 {zeta, znext}, {&c.ml, &c.mn}});
+      S.rounds[r + 1].push_back(VMat{c.log_n, ONE, (int)c.perml.size(), 2, {zeta, znext}, {&c.perml, &c.permn}});
+      const uint32_t w2n = two_adic_gen(c.log_n + 1);
+      for (int k = 0; k < 2; k++)
+        S.rounds[r + 2].push_back(VMat{c.log_n, mmul(to_mont(3), k ? w2n : ONE), 4, 1, {zeta, zeta},
+                                       {&c.q[k], &c.q[k]}});
+    }
+    S.roots[r] = pf.main_root.data();
+    S.roots[r + 1] = pf.perm_root.data();
+    S.roots[r + 2] = pf.quot_root.data();
+    S.nrounds = r + 3;
+    // ---- the sum of the cumulative sums (verifier.rs:210-213).  The reference checks it last; here
+    // it comes before the out-of-domain check, because that one can never be passed with a sum
+    // the prover did not commit to (every sum enters the transcript before alpha and the last-row
+    // constraint reads it): taken last, the check would name a changed sum as an OOD mismatch.
+    // The set of accepted proofs is the same either way.
+    {
+      EF total = ef_zero();
+      for (uint32_t i = 0; i < nc; i++) total = ef_add(total, co[i].cumsum);
+      if (!ef_is_zero(total)) throw std::runtime_error("cumulative sums do not sum to zero");
+    }
+    // ---- the out-of-domain check per chip (verifier.rs:194-213), in Chip::eval's order: the AIR's
+    // constraints, then the permutation constraints, folded with alpha
+    EF pb_pows[8];
+    pb_pows[0] = ef_one();
+    for (int j = 1; j < 8; j++) pb_pows[j] = ef_mul(pb_pows[j - 1], S.pb);
+    for (uint32_t i = 0; i < nc; i++) {
+      const ChipOpen& c = co[i];
+      const MachineChip& mc = m.chips[chip[i]];
+      const int n_log = c.log_n;
+      const uint32_t w2n = two_adic_gen(n_log + 1);
+      const uint32_t sh[2] = {to_mont(3), mmul(to_mont(3), w2n)};
+      EF quot = ef_zero();
+      for (int a = 0; a < 2; a++) {
+        const int b = 1 - a;
+        const EF zps = ef_mul(zp_at(n_log, sh[b], zeta), ef_inv(zp_at(n_log, sh[b], ef_base(sh[a]))));
+        for (int e = 0; e < 4; e++) quot = ef_add(quot, ef_mul(ef_mul(zps, monomial(e)), c.q[a][e]));
+      }
+      const uint32_t gn_inv = minv(two_adic_gen(n_log));
+      EF zh = zeta;
+      for (int k = 0; k < n_log; k++) zh = ef_mul(zh, zh);
+      zh = ef_sub(zh, ef_one());
+      const EF first = ef_mul(zh, ef_inv(ef_sub(zeta, ef_one())));
+      const EF last = ef_mul(zh, ef_inv(ef_sub(zeta, ef_base(gn_inv))));
+      const EF trans = ef_sub(zeta, ef_base(gn_inv));
+      const int pw = mc.p.perm_width();
+      std::vector<EF> perml(pw), permn(pw);
+      for (int e = 0; e < pw; e++) {
+        perml[e] = permn[e] = ef_zero();
+        for (int k = 0; k < 4; k++) {
+          perml[e] = ef_add(perml[e], ef_mul(monomial(k), c.perml[4 * e + k]));
+          permn[e] = ef_add(permn[e], ef_mul(monomial(k), c.permn[4 * e + k]));
+        }
+      }
+      std::vector<EF> cons((size_t)mc.p.num_constraints());
+      if (mc.p.has_air)
+        air_eval_ef(mc.p.air, c.ml.data(), c.mn.data(), first, last, trans, cons.data());
+      chip_perm_eval_ef(mc.p.lk, c.ml.data(), c.pl.data(), perml.data(), permn.data(), S.pa, pb_pows,
+                        c.cumsum, first, last, trans, cons.data() + mc.p.air_constraints());
+      EF folded = ef_zero();
+      for (const EF& v : cons) folded = ef_add(ef_mul(folded, S.alpha), v);
+      if (!ef_eq(ef_mul(folded, ef_inv(zh)), quot))
+        throw std::runtime_error("OOD evaluation mismatch on chip " + mc.name);
+    }
+    // ---- the PCS verification (TwoAdicFriPcs::verify): its transcript, then verify's query loop
+    pcs_transcript(S, ch, opt.observe_openings, opt.num_queries);
+    for (uint32_t q = 0; q < S.nq; q++) {
+      o.query = (int)q;
+      check_query(S, q);
+    }
+    o.query = -1;
+    o.ok = true;
+  } catch (const std::exception& e) {
+    o.why = e.what();
+  }
+  return o;
+}
+
 
 // Columns a chip's constraints read at the next row (quotient.rs:41-42), found by perturbing
 // one next-row value at a time in a random evaluation of fold_any (a column the constraints do
