@@ -620,6 +620,14 @@ extern "C" {
                              proof: *mut *mut u8, proof_len: *mut usize) -> c_int;
     pub fn bfz_machine_verify(m: *const bfz_machine, ch: *mut bfz_challenger, proof: *const u8,
                               proof_len: usize, out: *mut bfz_verify_outcome) -> c_int;
+    /// `bfz_machine_verify` of many proofs, each with its own challenger; `on_device = 1` runs
+    /// all their query phases in one device pass.
+    pub fn bfz_machine_verify_batch(m: *const bfz_machine, chs: *mut bfz_challenger,
+                                    proofs: *const *const u8, lens: *const usize, n: usize,
+                                    on_device: c_int, out: *mut bfz_verify_outcome) -> c_int;
+    pub fn bfz_machine_verify_time(m: *const bfz_machine, chs: *mut bfz_challenger,
+                                   proofs: *const *const u8, lens: *const usize, n: usize,
+                                   runs: c_int, ms: *mut f32) -> c_int;
     pub fn bfz_machine_time(m: *const bfz_machine, chips: *const c_int, traces: *const *const u32,
                             heights: *const usize, n: usize, runs: c_int, perm_ms: *mut f32,
                             quot_ms: *mut f32) -> c_int;

@@ -961,6 +961,25 @@ int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const u
  *                        ("cumulative sums do not sum to zero"; before the out-of-domain check, so
  *                        that a changed sum is named as such), per chip the out-of-domain check
  *                        ("OOD evaluation mismatch on chip NAME"), the PCS verification.
+ *   bfz_machine_verify_batch  bfz_machine_verify of n proofs of one machine, with
+ *                        bfz_verify_batch's contract: chs[i] is proof i's challenger after
+ *                        bfz_machine_observe and is advanced as bfz_machine_verify advances it;
+ *                        out[i] = (ok, query, why).  on_device = 0 is bfz_machine_verify proof by
+ *                        proof and touches no device.  on_device = 1 runs the query phase of all n
+ *                        proofs -- the input-round Merkle openings, the reduced openings, the fold
+ *                        chain, the commit-phase openings -- in one batched device pass
+ *                        (csrc/verify_machine.hip; a verifier-only machine may use it once
+ *                        bfz_init has bound a device) and everything else on the host in
+ *                        bfz_machine_verify's order, with the same outcomes and ending
+ *                        challengers for the same bytes.  Returns 0 whenever the check ran; a
+ *                        negative value for NULL arguments, for on_device = 1 without a bound
+ *                        device, or for a device error.  n = 0 is a no-op.
+ *   bfz_machine_verify_time  diagnostic (scripts/machine_verify_time.py): the device pass of
+ *                        bfz_machine_verify_batch over n accepted proofs (one batch), then its
+ *                        launches repeated over the same uploaded batch with HIP events around
+ *                        each: ms[5 * r + k] for run r < runs, k = clearing the reduced-openings
+ *                        workspace, k_mverify_reduce, k_mverify_fold, k_mverify_paths,
+ *                        k_mverify_inputs.  chs are read, not advanced.
  *   bfz_machine_time     diagnostic (scripts/machine_prove_time.py): HIP-event times, in ms, of
  *                        the segmented launches (k_perm_rows_machine, k_quotient_machine: one
  *                        launch over every chip) against the loop of per-chip launches
@@ -982,6 +1001,12 @@ int bfz_machine_prove(const bfz_machine* m, const int* chips, const uint32_t* co
                       size_t* proof_len);
 int bfz_machine_verify(const bfz_machine* m, bfz_challenger* ch, const uint8_t* proof,
                        size_t proof_len, bfz_verify_outcome* out);
+int bfz_machine_verify_batch(const bfz_machine* m, bfz_challenger* chs,
+                             const uint8_t* const* proofs, const size_t* lens, size_t n,
+                             int on_device, bfz_verify_outcome* out);
+int bfz_machine_verify_time(const bfz_machine* m, bfz_challenger* chs,
+                            const uint8_t* const* proofs, const size_t* lens, size_t n, int runs,
+                            float* ms);
 int bfz_machine_time(const bfz_machine* m, const int* chips, const uint32_t* const* traces,
                      const size_t* heights, size_t n, int runs, float* perm_ms, float* quot_ms);
 
@@ -996,11 +1021,11 @@ int bfz_set_pcs_variant(int observe_openings);
 
 /* Test-only fault injection, no reference counterpart: bit 0 perturbs the device challenger's
  * uploaded sponge state, so the host's replay of the device-sampled challenges must fail the
- * proof with "device transcript diverged" (tests/test_gpu.py).  Bit 1 makes bfz_verify_batch and
- * bfz_uni_verify_batch with on_device = 1 run their host side only (stages, packing, the queries
- * the packing keeps on the host) with a stand-in for the kernels that reports no failure and needs
- * no device, so that side is testable without a GPU (tests/test_verify_batch.py,
- * tests/test_uni_device.py); its verdicts are then not a verification.  Bit 2 cuts the key hash of the device path of bfz_*_debug_interactions, bfz_lookups_debug and
+ * proof with "device transcript diverged" (tests/test_gpu.py).  Bit 1 makes bfz_verify_batch,
+ * bfz_uni_verify_batch and bfz_machine_verify_batch with on_device = 1 run their host side only
+ * (stages, packing, the queries the packing keeps on the host) with a stand-in for the kernels
+ * that reports no failure and needs no device, so that side is testable without a GPU
+ * (tests/test_verify_batch.py, tests/test_uni_device.py); its verdicts are then not a verification.  Bit 2 cuts the key hash of the device path of bfz_*_debug_interactions, bfz_lookups_debug and
  * bfz_lookups_multiplicities to its low
  * 12 bits before anything uses it (home slot and tag alike), so distinct keys share tags and the
  * multi-round path runs; verdicts and records must not change.  0 (default) = off. */

@@ -329,6 +329,12 @@ SIGNATURES = [
                                   POINTER(POINTER(c_uint8)), POINTER(c_size_t)]),
     ("bfz_machine_verify", c_int, [c_void_p, POINTER(Challenger), POINTER(c_uint8), c_size_t,
                                    POINTER(VerifyOutcomeC)]),
+    ("bfz_machine_verify_batch", c_int, [c_void_p, POINTER(Challenger), POINTER(POINTER(c_uint8)),
+                                         POINTER(c_size_t), c_size_t, c_int,
+                                         POINTER(VerifyOutcomeC)]),
+    ("bfz_machine_verify_time", c_int, [c_void_p, POINTER(Challenger), POINTER(POINTER(c_uint8)),
+                                        POINTER(c_size_t), c_size_t, c_int,
+                                        POINTER(ctypes.c_float)]),
     ("bfz_machine_time", c_int, [c_void_p, POINTER(c_int), POINTER(POINTER(c_uint32)),
                                  POINTER(c_size_t), c_size_t, c_int, POINTER(ctypes.c_float),
                                  POINTER(ctypes.c_float)]),

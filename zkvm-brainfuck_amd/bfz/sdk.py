@@ -1798,6 +1798,49 @@ class Machine:
         check(lib().bfz_machine_verify(self._h, ctypes.byref(ch), buf, n, ctypes.byref(out)))
         return VerifyOutcome(ok=bool(out.ok), query=out.query, why=out.why.decode())
 
+    def verify_batch(self, proofs, chs=None, on_device: bool = True) -> List[VerifyOutcome]:
+        """bfz_machine_verify_batch: verify of many proofs of this machine, proofs[i] against chs[i]
+        (the states after observe, each advanced; fresh ones through observe() when None).  A
+        rejected proof does not raise.  on_device=True runs all the proofs' query phases in one
+        batched GPU pass and needs a bound device (a verifier-only machine binds none itself:
+        bfz.init first); False is verify proof by proof.  Both give the same outcomes."""
+        raw = [bytes(p) for p in proofs]
+        k = len(raw)
+        if chs is not None and len(chs) != k:
+            raise ValueError("Machine.verify_batch: one challenger per proof")
+        given = chs if chs is not None else [self.observe() for _ in range(k)]
+        bufs = [u8buf(x) for x in raw]
+        arr = (ctypes.POINTER(ctypes.c_uint8) * max(k, 1))(
+            *[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b, _ in bufs])
+        lens = (ctypes.c_size_t * max(k, 1))(*[n for _, n in bufs])
+        carr = (Challenger * max(k, 1))()
+        for i, c in enumerate(given):
+            ctypes.memmove(ctypes.byref(carr[i]), ctypes.byref(c), ctypes.sizeof(Challenger))
+        out = (_lib.VerifyOutcomeC * max(k, 1))()
+        check(lib().bfz_machine_verify_batch(self._h, carr, arr, lens, k, int(bool(on_device)), out))
+        for i, c in enumerate(given):
+            ctypes.memmove(ctypes.byref(c), ctypes.byref(carr[i]), ctypes.sizeof(Challenger))
+        return [VerifyOutcome(ok=bool(out[i].ok), query=out[i].query, why=out[i].why.decode())
+                for i in range(k)]
+
+    def verify_time(self, proofs, runs: int = 20):
+        """bfz_machine_verify_time (diagnostic): HIP-event milliseconds of the device pass's
+        launches over the accepted proofs, {"clear_ro" | "reduce" | "fold" | "paths" | "inputs":
+        [runs values]}."""
+        raw = [bytes(p) for p in proofs]
+        k = len(raw)
+        bufs = [u8buf(x) for x in raw]
+        arr = (ctypes.POINTER(ctypes.c_uint8) * k)(
+            *[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b, _ in bufs])
+        lens = (ctypes.c_size_t * k)(*[n for _, n in bufs])
+        carr = (Challenger * k)()
+        for i in range(k):
+            ctypes.memmove(ctypes.byref(carr[i]), ctypes.byref(self.observe()), ctypes.sizeof(Challenger))
+        ms = (ctypes.c_float * (5 * runs))()
+        check(lib().bfz_machine_verify_time(self._h, carr, arr, lens, k, int(runs), ms))
+        return {nm: [ms[5 * r + j] for r in range(runs)]
+                for j, nm in enumerate(("clear_ro", "reduce", "fold", "paths", "inputs"))}
+
     def time(self, traces, runs: int = 20):
         """bfz_machine_time (diagnostic): per-launch HIP-event milliseconds, as
         {"perm": (segmented, loop), "quotient": (segmented, loop)}, `runs` each."""

@@ -33,6 +33,7 @@
 #include "quotient.h"
 #include "uni_stark.h"
 #include "verify.h"
+#include "verify_machine.h"
 
 struct bfz_pk {
   std::shared_ptr<const bfz::ProvingKey> pk;  // shared with the per-program setup cache
@@ -863,6 +864,17 @@ namespace {
 // The query phase of bfz_verify_batch and bfz_uni_verify_batch with on_device = 1.
 void query_runner_device(const bfz::QueryBatch& b, uint32_t* keys) {
   bfz::verify_queries_device(b, keys, bfz::stream());
+}
+// The query phase of bfz_machine_verify_batch with on_device = 1.
+void machine_query_runner_device(const bfz::QueryBatch& b, uint32_t* keys) {
+  bfz::machine_queries_device(b, keys, bfz::stream());
+}
+// bfz_machine_verify_time: the same pass, then its launches timed over the same batch.
+int g_time_runs = 0, g_time_batches = 0;
+float* g_time_ms = nullptr;
+void machine_query_runner_timed(const bfz::QueryBatch& b, uint32_t* keys) {
+  bfz::machine_queries_device(b, keys, bfz::stream());
+  if (g_time_batches++ == 0) bfz::machine_queries_time(b, g_time_runs, g_time_ms, bfz::stream());
 }
 // The stand-in runs no kernel and leaves every key at "no failure": what remains is the host side
 // of the device path (stages, packing, the queries the packing keeps on the host).
@@ -2101,6 +2113,60 @@ int bfz_machine_verify(const bfz_machine* m, bfz_challenger* ch, const uint8_t* 
     vo.observe_openings = o.observe_openings;
     to_c(bfz::machine_verify(*m->m, c, proof, len, vo), out);
     to_c(c, ch);
+    return 0;
+  });
+}
+
+int bfz_machine_verify_batch(const bfz_machine* m, bfz_challenger* chs, const uint8_t* const* proofs,
+                             const size_t* lens, size_t n, int on_device, bfz_verify_outcome* out) {
+  return guarded([&] {
+    if (!m) throw std::runtime_error("null argument");
+    if (n == 0) return 0;
+    if (!chs || !proofs || !lens || !out) throw std::runtime_error("null argument");
+    for (size_t i = 0; i < n; i++)
+      if (!proofs[i] && lens[i]) throw std::runtime_error("null proof");
+    const bool standin = on_device && (g_fault & 2);  // bfz_set_fault_injection bit 1 (tests only)
+    if (on_device && !standin && g_bound < 0)
+      throw std::runtime_error("machine_verify_batch: no device bound (bfz_init) for on_device = 1");
+    const bfz::ProveOptions o = opts();
+    bfz::VerifyOptions vo;
+    vo.num_queries = o.num_queries;
+    vo.observe_openings = o.observe_openings;
+    std::vector<bfz::Challenger> cs(n);
+    for (size_t i = 0; i < n; i++) cs[i] = from_c(&chs[i]);
+    const std::vector<bfz::VerifyOutcome> v = bfz::machine_verify_batch(
+        *m->m, cs.data(), proofs, lens, n, vo,
+        standin ? query_runner_none : on_device ? machine_query_runner_device : nullptr);
+    for (size_t i = 0; i < n; i++) {
+      to_c(v[i], &out[i]);
+      to_c(cs[i], &chs[i]);
+    }
+    return 0;
+  });
+}
+
+int bfz_machine_verify_time(const bfz_machine* m, bfz_challenger* chs, const uint8_t* const* proofs,
+                            const size_t* lens, size_t n, int runs, float* ms) {
+  return guarded([&] {
+    if (!m || !chs || !proofs || !lens || !ms || n == 0 || runs < 1)
+      throw std::runtime_error("null argument");
+    for (size_t i = 0; i < n; i++)
+      if (!proofs[i] && lens[i]) throw std::runtime_error("null proof");
+    if (g_bound < 0) throw std::runtime_error("machine_verify_time: no device bound (bfz_init)");
+    const bfz::ProveOptions o = opts();
+    bfz::VerifyOptions vo;
+    vo.num_queries = o.num_queries;
+    vo.observe_openings = o.observe_openings;
+    std::vector<bfz::Challenger> cs(n);
+    for (size_t i = 0; i < n; i++) cs[i] = from_c(&chs[i]);
+    g_time_runs = runs;  // (the API lock is held)
+    g_time_ms = ms;
+    g_time_batches = 0;
+    const std::vector<bfz::VerifyOutcome> v =
+        bfz::machine_verify_batch(*m->m, cs.data(), proofs, lens, n, vo, machine_query_runner_timed);
+    if (g_time_batches != 1) throw std::runtime_error("machine_verify_time: the proofs are not one device batch");
+    for (const bfz::VerifyOutcome& x : v)
+      if (!x.ok) throw std::runtime_error("machine_verify_time: a proof was rejected: " + x.why);
     return 0;
   });
 }

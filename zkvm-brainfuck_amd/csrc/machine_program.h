@@ -74,6 +74,14 @@ std::vector<uint8_t> machine_prove(const MachineProgram& m, const int* chips,
                                    Challenger& ch, const ProveOptions& opt);
 VerifyOutcome machine_verify(const MachineProgram& m, Challenger& ch, const uint8_t* proof,
                              size_t len, const VerifyOptions& opt);
+// verify_batch's contract (verifier.h) for machine proofs: chs[i] is proof i's challenger after
+// machine_observe.  run_queries == nullptr is machine_verify proof by proof; otherwise the query
+// loops of all proofs go to run_queries as one batch of MQProof descriptors (verify_machine.h),
+// with machine_verify's outcomes and ending challengers.
+std::vector<VerifyOutcome> machine_verify_batch(const MachineProgram& m, Challenger* chs,
+                                                const uint8_t* const* proofs, const size_t* lens,
+                                                size_t n, const VerifyOptions& opt,
+                                                QueryRunner run_queries);
 
 // Diagnostic (bfz_machine_time): single launches of the segmented kernels (form A) against the
 // loop of per-chip launches (form B) on the same device inputs, alternating after one warm-up of

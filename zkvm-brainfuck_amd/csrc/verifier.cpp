@@ -22,6 +22,7 @@
 #include "quotient.h"
 #include "uni_stark.h"
 #include "verify.h"
+#include "verify_machine.h"
 
 namespace bfz {
 
@@ -652,6 +653,176 @@ void pack_proof(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* fir
   std::memcpy(&W[B.desc_off() + (size_t)slot * (sizeof(VProof) / 4)], &D, sizeof D);
 }
 
+// pack_proof for a machine of caller-defined chips (verify_machine.h): the same record and the same
+// rule -- every offset, width and count comes from S, which machine_before_queries filled from the
+// machine's ChipPrograms and the validated log degrees -- with the rounds, height groups, heights
+// and coefficient vectors written as tables of the lengths the proof has.
+void pack_machine_proof(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* first_bad) {
+  const ShardProof& pf = *S.pf;
+  uint32_t nq = 0;
+  while (nq < S.nq && query_shape_ok(S, pf.queries[nq])) nq++;
+  *first_bad = nq;
+  MQProof D;
+  std::memset(&D, 0, sizeof D);
+  D.nq = nq;
+  D.log_max = (uint32_t)S.log_max;
+  D.ncommit = S.ncommit;
+  D.nrounds = (uint32_t)S.nrounds;
+  D.final_poly = S.final_poly;
+  if (S.nrounds < 1 || S.nrounds > MQ_MAX_ROUNDS) throw std::runtime_error("verify_batch: bad round count");
+  if (S.log_max < 1 || S.log_max > 24) throw std::runtime_error("verify_batch: log height out of range");
+  std::vector<uint32_t>& W = B.words;
+
+  // the record of one query: per round the rows in Merkle order and the path, then the steps
+  uint32_t rec = 0;
+  std::vector<int> ord[MQ_MAX_ROUNDS];            // Merkle order of each round's matrices
+  std::vector<uint32_t> mat_off[MQ_MAX_ROUNDS];   // record offset of matrix i's row
+  std::vector<uint32_t> groups[MQ_MAX_ROUNDS];    // (log height, total width) per height group
+  MQRound rd[MQ_MAX_ROUNDS];
+  std::memset(rd, 0, sizeof rd);
+  for (int rr = 0; rr < S.nrounds; rr++) {
+    const std::vector<VMat>& ms = S.rounds[rr];
+    if (ms.empty()) throw std::runtime_error("verify_batch: empty round");
+    ord[rr].resize(ms.size());
+    for (size_t i = 0; i < ms.size(); i++) ord[rr][i] = (int)i;
+    std::stable_sort(ord[rr].begin(), ord[rr].end(),
+                     [&](int a, int b) { return ms[a].log_n > ms[b].log_n; });
+    MQRound& R = rd[rr];
+    std::vector<uint32_t>& G = groups[rr];
+    R.rows_off = rec;
+    mat_off[rr].resize(ms.size());
+    for (int i : ord[rr]) {
+      const VMat& m = ms[i];
+      if (m.w < 0 || m.w > (1 << 20)) throw std::runtime_error("verify_batch: row width out of range");
+      const uint32_t lh = (uint32_t)(m.log_n + LOG_BLOWUP);
+      if (G.empty() || G[G.size() - 2] != lh) {
+        G.push_back(lh);
+        G.push_back(0);
+      }
+      G.back() += (uint32_t)m.w;
+      mat_off[rr][i] = rec;
+      rec += (uint32_t)m.w;
+    }
+    R.ngroups = (uint32_t)(G.size() / 2);
+    R.lb = G[0];
+    R.path_off = rec;
+    rec += 8 * R.lb;
+    std::memcpy(R.root, S.roots[rr], 32);
+  }
+  D.steps_off = rec;
+  for (uint32_t s = 0; s < S.ncommit; s++) rec += 4 + 8 * (uint32_t)(S.log_max - 1 - (int)s);
+  D.qstride = rec;
+
+  // data
+  D.idx_off = (uint32_t)W.size();
+  for (uint32_t q = 0; q < nq; q++) W.push_back((uint32_t)S.index[q]);
+  D.croot_off = (uint32_t)W.size();
+  for (uint32_t s = 0; s < S.ncommit; s++) W.insert(W.end(), pf.commit_roots[s].begin(), pf.commit_roots[s].end());
+  D.beta_off = (uint32_t)W.size();
+  for (uint32_t s = 0; s < S.ncommit; s++) put_ef(W, S.betas[s]);
+  auto put_words = [&](const void* p, size_t bytes) {
+    const uint32_t* w = static_cast<const uint32_t*>(p);
+    W.insert(W.end(), w, w + bytes / 4);
+  };
+  // the group tables, then the round table that points at them
+  for (int rr = 0; rr < S.nrounds; rr++) {
+    rd[rr].grp_off = (uint32_t)W.size();
+    W.insert(W.end(), groups[rr].begin(), groups[rr].end());
+  }
+  D.rd_off = (uint32_t)W.size();
+  put_words(rd, (size_t)S.nrounds * sizeof(MQRound));
+
+  // reduced openings: per LDE height the coefficient of every column at the two points, the
+  // columns in the verifier's order (round, then matrix), alpha^k running over (matrix, point,
+  // column) across the rounds; a round's matrices of one height are one run of the record
+  std::vector<int> heights;
+  for (int rr = 0; rr < S.nrounds; rr++)
+    for (const VMat& m : S.rounds[rr]) {
+      const int lh = m.log_n + LOG_BLOWUP;
+      if (std::find(heights.begin(), heights.end(), lh) == heights.end()) heights.push_back(lh);
+    }
+  D.nheights = (uint32_t)heights.size();
+  std::vector<MQHeight> hs(heights.size());
+  std::vector<EF> coef0, coef1;
+  for (size_t j = 0; j < heights.size(); j++) {
+    MQHeight& H = hs[j];
+    std::memset(&H, 0, sizeof H);
+    H.lh = (uint32_t)heights[j];
+    H.a0 = H.a1 = ef_zero();
+    H.z0 = S.zeta;
+    H.z1 = ef_mul_base(S.zeta, two_adic_gen(heights[j] - LOG_BLOWUP));
+    coef0.clear();
+    coef1.clear();
+    EF apow = ef_one();
+    int nseg = 0;
+    for (int rr = 0; rr < S.nrounds; rr++) {
+      uint32_t next_off = 0;  // where the round's run of this height goes on
+      bool open = false;
+      for (size_t i = 0; i < S.rounds[rr].size(); i++) {
+        const VMat& m = S.rounds[rr][i];
+        if (m.log_n + LOG_BLOWUP != heights[j]) continue;
+        if (!open) {
+          H.seg_c0[nseg] = (uint32_t)coef0.size();
+          H.seg_delta[nseg] = mat_off[rr][i] - (uint32_t)coef0.size();
+          nseg++;
+          open = true;
+        } else if (mat_off[rr][i] != next_off) {
+          throw std::runtime_error("verify_batch: a height's rows are not one run of the record");
+        }
+        next_off = mat_off[rr][i] + (uint32_t)m.w;
+        const size_t c0 = coef0.size();
+        coef0.resize(c0 + (size_t)m.w, ef_zero());
+        coef1.resize(c0 + (size_t)m.w, ef_zero());
+        for (int p = 0; p < m.np; p++) {
+          // every point of this height is zeta or zeta * g (the quotient chunks: zeta only)
+          const bool second = p == 1;
+          if (!ef_eq(m.pt[p], second ? H.z1 : H.z0)) throw std::runtime_error("verify_batch: unexpected opening point");
+          EF& a = second ? H.a1 : H.a0;
+          for (int c = 0; c < m.w; c++) {
+            (second ? coef1 : coef0)[c0 + (size_t)c] = apow;
+            a = ef_add(a, ef_mul(apow, (*m.v[p])[c]));
+            apow = ef_mul(apow, S.fri_alpha);
+          }
+        }
+      }
+      if (open && next_off > rd[rr].path_off) throw std::runtime_error("verify_batch: rows past their round");
+    }
+    H.ncols = (uint32_t)coef0.size();
+    for (int k = nseg; k < MQ_MAX_ROUNDS; k++) H.seg_c0[k] = H.ncols;
+    H.coef_off = (uint32_t)W.size();
+    put_words(coef0.data(), coef0.size() * sizeof(EF));
+    put_words(coef1.data(), coef1.size() * sizeof(EF));
+  }
+  D.ht_off = (uint32_t)W.size();
+  put_words(hs.data(), hs.size() * sizeof(MQHeight));
+
+  D.qbase = (uint32_t)W.size();
+  for (uint32_t q = 0; q < nq; q++) {
+    const QueryProof& qp = pf.queries[q];
+    for (int rr = 0; rr < S.nrounds; rr++) {
+      const BatchOpening& bo = qp.inputs[rr];
+      for (int i : ord[rr]) W.insert(W.end(), bo.rows[i].begin(), bo.rows[i].end());
+      for (const Digest& d : bo.path) W.insert(W.end(), d.begin(), d.end());
+    }
+    for (const CommitPhaseStep& st : qp.steps) {
+      put_ef(W, st.sibling);
+      for (const Digest& d : st.path) W.insert(W.end(), d.begin(), d.end());
+    }
+    if (W.size() != (size_t)D.qbase + (size_t)(q + 1) * D.qstride)
+      throw std::runtime_error("verify_batch: query record length mismatch");
+  }
+  if (W.size() >= ((size_t)1 << 31)) throw std::runtime_error("verify_batch: batch too large");
+  D.leaf_base = (uint32_t)B.leaf_words;
+  B.leaf_words += (size_t)nq * S.ncommit * 8;
+  D.ro_base = (uint32_t)B.ro_words;
+  B.ro_words += (size_t)nq * VQ_RO_SLOTS * 4;
+  B.max_nq = std::max(B.max_nq, nq);
+  B.max_ncommit = std::max(B.max_ncommit, S.ncommit);
+  B.max_nrounds = std::max(B.max_nrounds, (uint32_t)S.nrounds);
+  B.max_nheights = std::max(B.max_nheights, D.nheights);
+  std::memcpy(&W[B.desc_off() + (size_t)slot * (sizeof(MQProof) / 4)], &D, sizeof D);
+}
+
 const char* reason_of_stage(uint32_t stage) {
   if (stage < (uint32_t)VQ_STAGE_STEP0) return "input Merkle opening rejected";
   if (stage < (uint32_t)VQ_STAGE_FINAL) return "FRI commit-phase opening rejected";
@@ -684,10 +855,14 @@ namespace {
 // ShardState: Slot holds one decoded proof and its state `S`; stage(i, slot) decodes proof i and
 // runs everything before the query loop (throwing the reason of the first failed check),
 // after(i, slot) runs what follows the loop.  The query loops of the proofs that got through
-// stage are packed into one QueryBatch per chunk and handed to run_queries.
+// stage are packed into one QueryBatch per chunk and handed to run_queries.  pack writes one
+// descriptor of desc_words words per proof, the layout run_queries' kernels read (pack_proof and
+// VProof, or pack_machine_proof and MQProof).
+using Packer = void (*)(const ShardState& S, QueryBatch& B, uint32_t slot, uint32_t* first_bad);
 template <class Slot, class Stage, class After>
 std::vector<VerifyOutcome> batch_on_device(const size_t* lens, size_t n, QueryRunner run_queries,
-                                           Stage stage, After after) {
+                                           Stage stage, After after, Packer pack = pack_proof,
+                                           size_t desc_words = sizeof(VProof) / 4) {
   std::vector<VerifyOutcome> out(n);
   // the device pass takes the proofs in chunks that bound the packed batch (2^31 words at most)
   constexpr size_t CHUNK_PROOFS = 1024, CHUNK_BYTES = (size_t)512 << 20;
@@ -708,7 +883,7 @@ std::vector<VerifyOutcome> batch_on_device(const size_t* lens, size_t n, QueryRu
     }
     QueryBatch B;
     B.nproofs = (uint32_t)packed.size();
-    B.words.assign(B.desc_off() + packed.size() * (sizeof(VProof) / 4), 0);
+    B.words.assign(B.desc_off() + packed.size() * desc_words, 0);
     for (uint32_t s = 0; s < B.nproofs; s++) B.words[s] = VQ_NO_FAILURE;
     for (int b = 0; b < 32; b++) {
       const uint32_t g = b <= 24 ? two_adic_gen(b) : ONE;
@@ -721,18 +896,20 @@ std::vector<VerifyOutcome> batch_on_device(const size_t* lens, size_t n, QueryRu
       // such as a preprocessed chip whose claimed log degree is not its key's: more heights than
       // the descriptor holds) is that proof's matter, not the call's: its slot stays empty and
       // all its queries run on the host below, so it gets the host's reason.
-      const uint32_t max_nq = B.max_nq, max_ncommit = B.max_ncommit, max_nrounds = B.max_nrounds;
+      const uint32_t max_nq = B.max_nq, max_ncommit = B.max_ncommit, max_nrounds = B.max_nrounds,
+                     max_nheights = B.max_nheights;
       const size_t words = B.words.size(), leaf_words = B.leaf_words, ro_words = B.ro_words;
       try {
-        pack_proof(slots[packed[s]].S, B, s, &first_bad[s]);
+        pack(slots[packed[s]].S, B, s, &first_bad[s]);
       } catch (const std::exception&) {
         B.words.resize(words);
         B.max_nq = max_nq;
         B.max_ncommit = max_ncommit;
         B.max_nrounds = max_nrounds;
+        B.max_nheights = max_nheights;
         B.leaf_words = leaf_words;
         B.ro_words = ro_words;
-        std::fill_n(&B.words[B.desc_off() + (size_t)s * (sizeof(VProof) / 4)], sizeof(VProof) / 4, 0u);
+        std::fill_n(&B.words[B.desc_off() + (size_t)s * desc_words], desc_words, 0u);
         first_bad[s] = 0;
       }
     }
@@ -975,137 +1152,154 @@ std::vector<VerifyOutcome> uni_verify_batch(const int* chips, Challenger* chs,
 // ------------------------------------------------------------------ machines of chip programs
 // verify_shard (verifier.rs:27-216) for a machine of caller-defined chips (machine_program.h): the
 // shapes come from the machine's ChipPrograms, never from the proof; ch = the challenger after
-// machine_observe, advanced as far as the check got.
+// machine_observe, advanced as far as the check got.  As verify_shard it is in stages around the
+// query loop: machine_before_queries is everything up to it (the out-of-domain check included:
+// this verifier runs it before the PCS verification) and nothing follows it.  S refers into pf: a
+// MachineState stays where it was filled.
+namespace {
+struct MachineState {
+  ShardProof pf;
+  ShardState S;
+};
+
+void machine_before_queries(const MachineProgram& m, Challenger& ch, const uint8_t* proof, size_t len,
+                            const VerifyOptions& opt, MachineState& M) {
+  M.pf = decode_bfz1_machine(proof, len, m.names());
+  const ShardProof& pf = M.pf;
+  ShardState& S = M.S;
+  S.pf = &pf;
+  const uint32_t nc = (uint32_t)pf.chips.size();
+  const std::vector<int>& chip = pf.chips;  // indices into m.chips, distinct (the decoder)
+  std::vector<ChipOpen>& co = S.co;
+  co.reserve(nc);
+  std::vector<int> at_of(m.chips.size(), -1);  // machine chip -> position in the proof
+  for (uint32_t i = 0; i < nc; i++) {
+    const ChipOpened& ov = pf.opened[i];
+    const MachineChip& mc = m.chips[chip[i]];
+    if (ov.log_degree > 23) throw std::runtime_error("log degree out of range");
+    co.push_back(ChipOpen{(int)ov.log_degree, ov.prep_local, ov.prep_next, ov.main_local,
+                          ov.main_next, ov.perm_local, ov.perm_next, ov.quotient, ov.cumsum});
+    const ChipOpen& c = co.back();
+    const size_t pw = (size_t)mc.p.lk.prep_w;
+    if (c.ml.size() != (size_t)mc.p.lk.main_w || c.mn.size() != c.ml.size() ||
+        c.perml.size() != 4 * (size_t)mc.p.perm_width() || c.permn.size() != c.perml.size() ||
+        c.pl.size() != pw || c.pn.size() != pw || c.q[0].size() != 4 || c.q[1].size() != 4)
+      throw std::runtime_error("opened-value shape mismatch");
+    if (mc.local_only)  // (as before_queries: the prover's zeros are required)
+      for (const std::vector<EF>* v : {&c.pn, &c.mn})
+        for (const EF& e : *v)
+          if (e.c[0] | e.c[1] | e.c[2] | e.c[3])
+            throw std::runtime_error("local-only chip with non-zero next values");
+    if (pw && ((size_t)1 << c.log_n) != mc.prep_height)
+      throw std::runtime_error("log degree is not the preprocessed height of chip " + mc.name);
+    at_of[chip[i]] = (int)i;
+  }
+  // ---- transcript (verifier.rs:76-101)
+  ch.observe_digest(pf.main_root.data());
+  S.pa = ch.sample_ef();
+  S.pb = ch.sample_ef();
+  ch.observe_digest(pf.perm_root.data());
+  for (uint32_t i = 0; i < nc; i++) ch.observe_ef(co[i].cumsum);
+  S.alpha = ch.sample_ef();
+  ch.observe_digest(pf.quot_root.data());
+  const EF zeta = S.zeta = ch.sample_ef();
+
+  // ---- rounds for the PCS verification: preprocessed (when the machine has one), main,
+  // permutation, quotient
+  int r = 0;
+  if (m.has_prep) {
+    for (int pc : m.prep_chips) {
+      if (at_of[pc] < 0) throw std::runtime_error("preprocessed chip missing from proof");
+      const MachineChip& mc = m.chips[pc];
+      const ChipOpen& c = co[at_of[pc]];
+      S.rounds[0].push_back(VMat{c.log_n, ONE, mc.p.lk.prep_w, mc.local_only ? 1 : 2,
+                                 {zeta, ef_mul_base(zeta, two_adic_gen(c.log_n))}, {&c.pl, &c.pn}});
+    }
+    S.roots[0] = m.prep_root;
+    r = 1;
+  }
+  for (uint32_t i = 0; i < nc; i++) {
+    const ChipOpen& c = co[i];
+    const EF znext = ef_mul_base(zeta, two_adic_gen(c.log_n));
+    S.rounds[r].push_back(VMat{c.log_n, ONE, (int)c.ml.size(), m.chips[chip[i]].local_only ? 1 : 2,
+                               {zeta, znext}, {&c.ml, &c.mn}});
+    S.rounds[r + 1].push_back(VMat{c.log_n, ONE, (int)c.perml.size(), 2, {zeta, znext}, {&c.perml, &c.permn}});
+    const uint32_t w2n = two_adic_gen(c.log_n + 1);
+    for (int k = 0; k < 2; k++)
+      S.rounds[r + 2].push_back(VMat{c.log_n, mmul(to_mont(3), k ? w2n : ONE), 4, 1, {zeta, zeta},
+                                     {&c.q[k], &c.q[k]}});
+  }
+  S.roots[r] = pf.main_root.data();
+  S.roots[r + 1] = pf.perm_root.data();
+  S.roots[r + 2] = pf.quot_root.data();
+  S.nrounds = r + 3;
+  // ---- the sum of the cumulative sums (verifier.rs:210-213).  The reference checks it last; here
+  // it comes before the out-of-domain check, because that one can never be passed with a sum
+  // the prover did not commit to (every sum enters the transcript before alpha and the last-row
+  // constraint reads it): taken last, the check would name a changed sum as an OOD mismatch.
+  // The set of accepted proofs is the same either way.
+  {
+    EF total = ef_zero();
+    for (uint32_t i = 0; i < nc; i++) total = ef_add(total, co[i].cumsum);
+    if (!ef_is_zero(total)) throw std::runtime_error("cumulative sums do not sum to zero");
+  }
+  // ---- the out-of-domain check per chip (verifier.rs:194-213), in Chip::eval's order: the AIR's
+  // constraints, then the permutation constraints, folded with alpha
+  EF pb_pows[8];
+  pb_pows[0] = ef_one();
+  for (int j = 1; j < 8; j++) pb_pows[j] = ef_mul(pb_pows[j - 1], S.pb);
+  for (uint32_t i = 0; i < nc; i++) {
+    const ChipOpen& c = co[i];
+    const MachineChip& mc = m.chips[chip[i]];
+    const int n_log = c.log_n;
+    const uint32_t w2n = two_adic_gen(n_log + 1);
+    const uint32_t sh[2] = {to_mont(3), mmul(to_mont(3), w2n)};
+    EF quot = ef_zero();
+    for (int a = 0; a < 2; a++) {
+      const int b = 1 - a;
+      const EF zps = ef_mul(zp_at(n_log, sh[b], zeta), ef_inv(zp_at(n_log, sh[b], ef_base(sh[a]))));
+      for (int e = 0; e < 4; e++) quot = ef_add(quot, ef_mul(ef_mul(zps, monomial(e)), c.q[a][e]));
+    }
+    const uint32_t gn_inv = minv(two_adic_gen(n_log));
+    EF zh = zeta;
+    for (int k = 0; k < n_log; k++) zh = ef_mul(zh, zh);
+    zh = ef_sub(zh, ef_one());
+    const EF first = ef_mul(zh, ef_inv(ef_sub(zeta, ef_one())));
+    const EF last = ef_mul(zh, ef_inv(ef_sub(zeta, ef_base(gn_inv))));
+    const EF trans = ef_sub(zeta, ef_base(gn_inv));
+    const int pw = mc.p.perm_width();
+    std::vector<EF> perml(pw), permn(pw);
+    for (int e = 0; e < pw; e++) {
+      perml[e] = permn[e] = ef_zero();
+      for (int k = 0; k < 4; k++) {
+        perml[e] = ef_add(perml[e], ef_mul(monomial(k), c.perml[4 * e + k]));
+        permn[e] = ef_add(permn[e], ef_mul(monomial(k), c.permn[4 * e + k]));
+      }
+    }
+    std::vector<EF> cons((size_t)mc.p.num_constraints());
+    if (mc.p.has_air)
+      air_eval_ef(mc.p.air, c.ml.data(), c.mn.data(), first, last, trans, cons.data());
+    chip_perm_eval_ef(mc.p.lk, c.ml.data(), c.pl.data(), perml.data(), permn.data(), S.pa, pb_pows,
+                      c.cumsum, first, last, trans, cons.data() + mc.p.air_constraints());
+    EF folded = ef_zero();
+    for (const EF& v : cons) folded = ef_add(ef_mul(folded, S.alpha), v);
+    if (!ef_eq(ef_mul(folded, ef_inv(zh)), quot))
+      throw std::runtime_error("OOD evaluation mismatch on chip " + mc.name);
+  }
+  // ---- the PCS verification (TwoAdicFriPcs::verify): its transcript; verify's query loop follows
+  pcs_transcript(S, ch, opt.observe_openings, opt.num_queries);
+}
+}  // namespace
+
 VerifyOutcome machine_verify(const MachineProgram& m, Challenger& ch, const uint8_t* proof,
                              size_t len, const VerifyOptions& opt) {
   VerifyOutcome o;
   try {
-    const ShardProof pf = decode_bfz1_machine(proof, len, m.names());
-    ShardState S;
-    S.pf = &pf;
-    const uint32_t nc = (uint32_t)pf.chips.size();
-    const std::vector<int>& chip = pf.chips;  // indices into m.chips, distinct (the decoder)
-    std::vector<ChipOpen>& co = S.co;
-    co.reserve(nc);
-    std::vector<int> at_of(m.chips.size(), -1);  // machine chip -> position in the proof
-    for (uint32_t i = 0; i < nc; i++) {
-      const ChipOpened& ov = pf.opened[i];
-      const MachineChip& mc = m.chips[chip[i]];
-      if (ov.log_degree > 23) throw std::runtime_error("log degree out of range");
-      co.push_back(ChipOpen{(int)ov.log_degree, ov.prep_local, ov.prep_next, ov.main_local,
-                            ov.main_next, ov.perm_local, ov.perm_next, ov.quotient, ov.cumsum});
-      const ChipOpen& c = co.back();
-      const size_t pw = (size_t)mc.p.lk.prep_w;
-      if (c.ml.size() != (size_t)mc.p.lk.main_w || c.mn.size() != c.ml.size() ||
-          c.perml.size() != 4 * (size_t)mc.p.perm_width() || c.permn.size() != c.perml.size() ||
-          c.pl.size() != pw || c.pn.size() != pw || c.q[0].size() != 4 || c.q[1].size() != 4)
-        throw std::runtime_error("opened-value shape mismatch");
-      if (mc.local_only)  // (as before_queries: the prover's zeros are required)
-        for (const std::vector<EF>* v : {&c.pn, &c.mn})
-          for (const EF& e : *v)
-            if (e.c[0] | e.c[1] | e.c[2] | e.c[3])
-              throw std::runtime_error("local-only chip with non-zero next values");
-      if (pw && ((size_t)1 << c.log_n) != mc.prep_height)
-        throw std::runtime_error("log degree is not the preprocessed height of chip " + mc.name);
-      at_of[chip[i]] = (int)i;
-    }
-    // ---- transcript (verifier.rs:76-101)
-    ch.observe_digest(pf.main_root.data());
-    S.pa = ch.sample_ef();
-    S.pb = ch.sample_ef();
-    ch.observe_digest(pf.perm_root.data());
-    for (uint32_t i = 0; i < nc; i++) ch.observe_ef(co[i].cumsum);
-    S.alpha = ch.sample_ef();
-    ch.observe_digest(pf.quot_root.data());
-    const EF zeta = S.zeta = ch.sample_ef();
-
-    // ---- rounds for the PCS verification: preprocessed (when the machine has one), main,
-    // permutation, quotient
-    int r = 0;
-    if (m.has_prep) {
-      for (int pc : m.prep_chips) {
-        if (at_of[pc] < 0) throw std::runtime_error("preprocessed chip missing from proof");
-        const MachineChip& mc = m.chips[pc];
-        const ChipOpen& c = co[at_of[pc]];
-        S.rounds[0].push_back(VMat{c.log_n, ONE, mc.p.lk.prep_w, mc.local_only ? 1 : 2,
-                                   {zeta, ef_mul_base(zeta, two_adic_gen(c.log_n))}, {&c.pl, &c.pn}});
-      }
-      S.roots[0] = m.prep_root;
-      r = 1;
-    }
-    for (uint32_t i = 0; i < nc; i++) {
-      const ChipOpen& c = co[i];
-      const EF znext = ef_mul_base(zeta, two_adic_gen(c.log_n));
-      S.rounds[r].push_back(VMat{c.log_n, ONE, (int)c.ml.size(), m.chips[chip[i]].local_only ? 1 : 2,
-                                 {zeta, znext}, {&c.ml, &c.mn}});
-      S.rounds[r + 1].push_back(VMat{c.log_n, ONE, (int)c.perml.size(), 2, {zeta, znext}, {&c.perml, &c.permn}});
-      const uint32_t w2n = two_adic_gen(c.log_n + 1);
-      for (int k = 0; k < 2; k++)
-        S.rounds[r + 2].push_back(VMat{c.log_n, mmul(to_mont(3), k ? w2n : ONE), 4, 1, {zeta, zeta},
-                                       {&c.q[k], &c.q[k]}});
-    }
-    S.roots[r] = pf.main_root.data();
-    S.roots[r + 1] = pf.perm_root.data();
-    S.roots[r + 2] = pf.quot_root.data();
-    S.nrounds = r + 3;
-    // ---- the sum of the cumulative sums (verifier.rs:210-213).  The reference checks it last; here
-    // it comes before the out-of-domain check, because that one can never be passed with a sum
-    // the prover did not commit to (every sum enters the transcript before alpha and the last-row
-    // constraint reads it): taken last, the check would name a changed sum as an OOD mismatch.
-    // The set of accepted proofs is the same either way.
-    {
-      EF total = ef_zero();
-      for (uint32_t i = 0; i < nc; i++) total = ef_add(total, co[i].cumsum);
-      if (!ef_is_zero(total)) throw std::runtime_error("cumulative sums do not sum to zero");
-    }
-    // ---- the out-of-domain check per chip (verifier.rs:194-213), in Chip::eval's order: the AIR's
-    // constraints, then the permutation constraints, folded with alpha
-    EF pb_pows[8];
-    pb_pows[0] = ef_one();
-    for (int j = 1; j < 8; j++) pb_pows[j] = ef_mul(pb_pows[j - 1], S.pb);
-    for (uint32_t i = 0; i < nc; i++) {
-      const ChipOpen& c = co[i];
-      const MachineChip& mc = m.chips[chip[i]];
-      const int n_log = c.log_n;
-      const uint32_t w2n = two_adic_gen(n_log + 1);
-      const uint32_t sh[2] = {to_mont(3), mmul(to_mont(3), w2n)};
-      EF quot = ef_zero();
-      for (int a = 0; a < 2; a++) {
-        const int b = 1 - a;
-        const EF zps = ef_mul(zp_at(n_log, sh[b], zeta), ef_inv(zp_at(n_log, sh[b], ef_base(sh[a]))));
-        for (int e = 0; e < 4; e++) quot = ef_add(quot, ef_mul(ef_mul(zps, monomial(e)), c.q[a][e]));
-      }
-      const uint32_t gn_inv = minv(two_adic_gen(n_log));
-      EF zh = zeta;
-      for (int k = 0; k < n_log; k++) zh = ef_mul(zh, zh);
-      zh = ef_sub(zh, ef_one());
-      const EF first = ef_mul(zh, ef_inv(ef_sub(zeta, ef_one())));
-      const EF last = ef_mul(zh, ef_inv(ef_sub(zeta, ef_base(gn_inv))));
-      const EF trans = ef_sub(zeta, ef_base(gn_inv));
-      const int pw = mc.p.perm_width();
-      std::vector<EF> perml(pw), permn(pw);
-      for (int e = 0; e < pw; e++) {
-        perml[e] = permn[e] = ef_zero();
-        for (int k = 0; k < 4; k++) {
-          perml[e] = ef_add(perml[e], ef_mul(monomial(k), c.perml[4 * e + k]));
-          permn[e] = ef_add(permn[e], ef_mul(monomial(k), c.permn[4 * e + k]));
-        }
-      }
-      std::vector<EF> cons((size_t)mc.p.num_constraints());
-      if (mc.p.has_air)
-        air_eval_ef(mc.p.air, c.ml.data(), c.mn.data(), first, last, trans, cons.data());
-      chip_perm_eval_ef(mc.p.lk, c.ml.data(), c.pl.data(), perml.data(), permn.data(), S.pa, pb_pows,
-                        c.cumsum, first, last, trans, cons.data() + mc.p.air_constraints());
-      EF folded = ef_zero();
-      for (const EF& v : cons) folded = ef_add(ef_mul(folded, S.alpha), v);
-      if (!ef_eq(ef_mul(folded, ef_inv(zh)), quot))
-        throw std::runtime_error("OOD evaluation mismatch on chip " + mc.name);
-    }
-    // ---- the PCS verification (TwoAdicFriPcs::verify): its transcript, then verify's query loop
-    pcs_transcript(S, ch, opt.observe_openings, opt.num_queries);
-    for (uint32_t q = 0; q < S.nq; q++) {
+    MachineState M;
+    machine_before_queries(m, ch, proof, len, opt, M);
+    for (uint32_t q = 0; q < M.S.nq; q++) {
       o.query = (int)q;
-      check_query(S, q);
+      check_query(M.S, q);
     }
     o.query = -1;
     o.ok = true;
@@ -1113,6 +1307,21 @@ VerifyOutcome machine_verify(const MachineProgram& m, Challenger& ch, const uint
     o.why = e.what();
   }
   return o;
+}
+
+std::vector<VerifyOutcome> machine_verify_batch(const MachineProgram& m, Challenger* chs,
+                                                const uint8_t* const* proofs, const size_t* lens,
+                                                size_t n, const VerifyOptions& opt,
+                                                QueryRunner run_queries) {
+  if (!run_queries) {
+    std::vector<VerifyOutcome> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = machine_verify(m, chs[i], proofs[i], lens[i], opt);
+    return out;
+  }
+  return batch_on_device<MachineState>(
+      lens, n, run_queries,
+      [&](size_t i, MachineState& M) { machine_before_queries(m, chs[i], proofs[i], lens[i], opt, M); },
+      [](size_t, const MachineState&) {}, pack_machine_proof, sizeof(MQProof) / 4);
 }
 
 

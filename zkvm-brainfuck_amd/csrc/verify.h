@@ -75,6 +75,7 @@ struct QueryBatch {
   std::vector<uint32_t> words;  // the layout above
   uint32_t nproofs = 0;
   uint32_t max_nq = 0, max_ncommit = 0, max_nrounds = 0;
+  uint32_t max_nheights = 0;  // machine batches (verify_machine.h): most LDE heights of one proof
   size_t leaf_words = 0, ro_words = 0;  // workspace sizes
   size_t desc_off() const { return (size_t)nproofs + 64; }
 };
