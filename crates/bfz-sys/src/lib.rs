@@ -655,6 +655,8 @@ extern "C" {
     pub fn bfz_ntt_last_paths(mask_out: *mut u32) -> c_int;
     pub fn bfz_commit(mats: *const *const u32, heights: *const usize, widths: *const usize,
                       nmats: usize, root: *mut u32) -> c_int;
+    pub fn bfz_merkle_time(rows: usize, widths: *const c_int, nmats: usize, kind_a: c_int,
+                           kind_b: c_int, runs: c_int, ms_a: *mut f32, ms_b: *mut f32) -> c_int;
     pub fn bfz_poseidon2_permute(states: *mut u32, n: usize) -> c_int;
     pub fn bfz_poseidon2_permute_small(states: *mut u32, n: usize) -> c_int;
 }

@@ -948,8 +948,8 @@ int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const u
  *                        = its main trace, heights[i] a power of two in [1, 2^23]; words >= p are
  *                        refused with bfz_uni_prove's message.  A chip with preprocessed columns
  *                        must be included, at its preprocessed height.  At most 8 included chips
- *                        may share one height (a commit hashes at most 16 matrices of one height
- *                        and the quotient round has two per chip); more are refused before any
+ *                        may share one height (the machine prover's own limit; a commit takes any
+ *                        number of matrices at any heights); more are refused before any
  *                        device work with "machine: N chips of height H, a proof takes at most 8
  *                        of one height".  bfz_machine_time has no such bound (it builds no
  *                        trees).  ch is advanced as by
@@ -1076,8 +1076,18 @@ int bfz_lde_shard(const uint32_t* evals, size_t n, size_t w, uint32_t shift, int
                   int flags, uint32_t* coef_out, uint32_t* shard_out, uint32_t* next_out,
                   int* dft_low_out);
 int bfz_ntt_last_paths(uint32_t* mask_out);
+/* Any number of matrices at any power-of-two heights: a launch whose column list has more than 16
+ * matrices reads it from the tree's column table in device memory (csrc/merkle.hip). */
 int bfz_commit(const uint32_t* const* mats, const size_t* heights, const size_t* widths,
                size_t nmats, uint32_t root[8]);
+/* Diagnostic (scripts/merkle_wide_time.py): HIP-event times, in ms, of single launches of two
+ * Merkle kernels on the same generated device matrices (nmats of `rows` rows, rows a power of two
+ * up to 2^24), alternating, `runs` of each after one warm-up of each; their digests are compared.
+ * Kinds: 0 / 1 = k_hash_leaves with the list in the kernel arguments / in a column table, 2 / 3 =
+ * k_hash_leaves_lanes likewise, 4 / 5 = the layer launch of `rows` nodes that injects the
+ * matrices (k_compress above 2^14 nodes).  Both kinds are leaf kinds or both layer kinds. */
+int bfz_merkle_time(size_t rows, const int* widths, size_t nmats, int kind_a, int kind_b, int runs,
+                    float* ms_a, float* ms_b);
 int bfz_poseidon2_permute(uint32_t* states, size_t n);
 /* The latency-optimised form used for small Merkle layers (16 lanes per state, DPP). */
 int bfz_poseidon2_permute_small(uint32_t* states, size_t n);

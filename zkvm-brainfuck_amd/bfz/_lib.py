@@ -356,6 +356,8 @@ SIGNATURES = [
     ("bfz_ntt_last_paths", c_int, [POINTER(c_uint32)]),
     ("bfz_commit", c_int, [POINTER(POINTER(c_uint32)), POINTER(c_size_t), POINTER(c_size_t),
                            c_size_t, POINTER(c_uint32)]),
+    ("bfz_merkle_time", c_int, [c_size_t, POINTER(c_int), c_size_t, c_int, c_int, c_int,
+                                POINTER(ctypes.c_float), POINTER(ctypes.c_float)]),
     ("bfz_poseidon2_permute", c_int, [POINTER(c_uint32), c_size_t]),
     ("bfz_poseidon2_permute_small", c_int, [POINTER(c_uint32), c_size_t]),
 ]

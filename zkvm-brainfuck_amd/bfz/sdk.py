@@ -1693,8 +1693,8 @@ class Machine:
     Montgomery words).  With every preprocessed trace given (or none needed) the traces are
     committed on the device and the machine proves and verifies; with prep_root (8 Montgomery
     words) and prep_heights ({name: height}) instead, it only verifies and touches no device.
-    Up to 32 chips; a proof takes at most 8 chips of one height (the Merkle commit hashes at most
-    16 matrices of one height and the quotient round has two per chip) and prove refuses more."""
+    Up to 32 chips; a proof takes at most 8 chips of one height (the machine prover's own limit:
+    the Merkle commit takes any number of matrices at any heights) and prove refuses more."""
 
     def __init__(self, chips, prep_root=None, prep_heights=None):
         import numpy as np

@@ -2831,6 +2831,14 @@ int bfz_commit(const uint32_t* const* mats, const size_t* heights, const size_t*
   });
 }
 
+int bfz_merkle_time(size_t rows, const int* widths, size_t nmats, int kind_a, int kind_b, int runs,
+                    float* ms_a, float* ms_b) {
+  return guarded([&] {
+    bfz::merkle_time(rows, widths, nmats, kind_a, kind_b, runs, ms_a, ms_b);
+    return 0;
+  });
+}
+
 int bfz_poseidon2_permute(uint32_t* states, size_t n) {
   return guarded([&] {
     hipStream_t st = bfz::stream();

@@ -24,8 +24,8 @@
 namespace bfz {
 
 constexpr int MACHINE_MAX_CHIPS = BFZ_MACHINE_MAX_CHIPS;
-// Included chips of one height in a proof: a commit hashes at most 16 matrices of one height
-// (merkle.hip) and the quotient round has two chunks per chip.
+// Included chips of one height in a proof: the machine prover's own limit (a commit takes any
+// number of matrices at any heights, merkle.hip).
 constexpr size_t MACHINE_MAX_SAME_HEIGHT = 8;
 
 struct MachineChip {

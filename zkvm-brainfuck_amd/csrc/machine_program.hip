@@ -264,7 +264,7 @@ struct Prover {
       if (!seen[pc])
         throw std::runtime_error("machine: chip " + m.chips[pc].name +
                                  " has preprocessed columns and must be included");
-    if (tree)  // a commit hashes at most 16 matrices of one height (merkle.hip): two chunks per chip
+    if (tree)  // the machine prover's own limit (the commit has none, merkle.hip)
       for (size_t i = 0; i < n; i++) {
         size_t same = 0;
         for (size_t j = 0; j < n; j++) same += heights[j] == heights[i];
@@ -608,8 +608,8 @@ void machine_time(const MachineProgram& m, const int* chips, const uint32_t* con
   CallEnd end{st};
   Prover P(m, st);
   // The LDEs without the Merkle trees, which neither form reads: the challenges come from the
-  // transcript head alone (a commit holds at most 16 matrices of one height, merkle.hip; the
-  // launches measured here have no such bound).
+  // transcript head alone (a proof takes at most MACHINE_MAX_SAME_HEIGHT chips of one height, the
+  // launches measured here any number).
   Challenger ch;
   machine_observe(m, ch);
   P.commit_main(chips, traces, heights, n, /*tree=*/false);

@@ -16,9 +16,21 @@ struct MatRef {           // column-major, bit-reversed rows
   size_t stride = 0;
 };
 
+// One matrix's columns as the hashing kernels walk them ("segment"): column k is at
+// base + k * stride, n >= 1 columns.
+struct ColSeg {
+  const uint32_t* base;
+  size_t stride;
+  int n;
+};
+
 struct MerkleTree {
   std::vector<DBuf<uint32_t>> layers;  // layers[L]: (max_height >> L) digests x 8 (Montgomery)
   std::vector<MatRef> mats;            // committed matrices in commit order
+  // The tree's column table: every matrix's segment, heights descending (the order they are
+  // hashed in).  Built only for a tree with more segments than a launch's kernel arguments hold
+  // (merkle.hip, MAXSEG); each tree has its own, since several proofs are in flight on lanes.
+  DBuf<ColSeg> col_table;
   uint32_t root[8];                    // Montgomery form
   int sharded_below = 0;               // layers [0, sharded_below) hold only this rank's range
   int shard_log = 0;                   // log2(world) when sharded
@@ -54,6 +66,15 @@ ShardCtx*& shard_ctx();
 // fetch_root = false the root stays on the device, tree.layers.back(), tree.root not filled).
 void merkle_build(const std::vector<MatRef>& mats, MerkleTree& tree, hipStream_t st,
                   bool fetch_root = true);
+
+// Diagnostic (bfz_merkle_time): HIP-event times, in ms, of single launches of two Merkle kernels
+// on the same device inputs (nmats generated matrices of `rows` rows), alternating, `runs` of
+// each after one warm-up of each.  Kinds: 0 / 1 leaves by threads (k_hash_leaves), list in the
+// kernel arguments / in a column table; 2 / 3 leaves in lane mode (k_hash_leaves_lanes); 4 / 5
+// the layer launch of `rows` nodes injecting the matrices.  Both kinds are leaf kinds or both
+// layer kinds; throws if their digests differ.
+void merkle_time(size_t rows, const int* widths, size_t nmats, int kind_a, int kind_b, int runs,
+                 float* ms_a, float* ms_b);
 
 // Batched Poseidon2 permutations of n 16-element states in place (device pointer).
 void poseidon2_batch(uint32_t* states, size_t n, hipStream_t st);
