@@ -634,6 +634,8 @@ extern "C" {
 
     pub fn bfz_set_num_queries(num_queries: c_int) -> c_int;
     pub fn bfz_set_pcs_variant(observe_openings: c_int) -> c_int;
+    /// The largest constraint degree the `bfz_air_*` calls accept: 3..=9, 0 = the default (3).
+    pub fn bfz_set_air_max_degree(degree: c_int) -> c_int;
     /// Test-only fault injection (bit 0: perturb the device challenger); 0 = off.
     pub fn bfz_set_fault_injection(mask: c_int) -> c_int;
 

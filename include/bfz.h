@@ -695,8 +695,11 @@ int bfz_uni_verify_batch(const int* chips, bfz_challenger* chs, const uint8_t* c
  * constant 0, is_first_row / is_last_row 1, is_transition 0, add / sub the maximum, mul the sum,
  * neg the identity; the AIR's degree is the maximum, log_quotient_degree = log2_ceil(degree - 1).
  * Every call validates the program first (a malformed one: negative status, the message names the
- * word offset) and refuses a degree above 3 and a program whose compiled instruction list keeps
- * more than BFZ_AIR_MAX_LIVE values live at once (the message names the count).
+ * word offset) and refuses a degree above the cap in force -- 3 unless bfz_set_air_max_degree
+ * (below) raised it, 9 at most -- and a program whose compiled instruction list keeps more than
+ * BFZ_AIR_MAX_LIVE values live at once (the message names the count).  From degree 4 the quotient
+ * has 4 or 8 chunks and lives on 3 H_(4n) or 3 H_(8n), which the prover evaluates one coset of
+ * 3 H_2n at a time; the row checks do not depend on the degree.
  *
  *   bfz_air_export  host only: the BFA1 program of a built-in chip's AIR (the chips of
  *                   bfz_uni_info, the same refusals); *prog is freed with bfz_free.  Proofs and
@@ -1018,6 +1021,16 @@ int bfz_set_num_queries(int num_queries);
  * challenge alpha is sampled (default), 0 = alpha is sampled first; -1 = environment
  * BFZ_OBSERVE_OPENINGS.  Applies to bfz_prove*, bfz_verify*, identically in the oracle. */
 int bfz_set_pcs_variant(int observe_openings);
+
+/* The largest constraint degree the bfz_air_* calls accept: 3..9, or 0 = the default, 3; any
+ * other value is an error that names the "max degree".  Process-wide, like the two switches
+ * above.  A program above the cap in force is refused by every bfz_air_* call, bfz_air_verify
+ * included, with "uni_stark: constraint degree above <cap> is not supported".  Degrees 4 and 5
+ * give log_quotient_degree 2 (4 quotient chunks), 6 to 9 give 3 (8 chunks); the height is then at
+ * most 2^(24 - log_quotient_degree).  Nothing else is opted in: the built-in chips are what they
+ * are, and chip programs and machines (bfz_chip_*, bfz_machine_*) keep their own refusal of an
+ * AIR degree above 3 and stay at log quotient degree 1 whatever this switch says. */
+int bfz_set_air_max_degree(int degree);
 
 /* Test-only fault injection, no reference counterpart: bit 0 perturbs the device challenger's
  * uploaded sponge state, so the host's replay of the device-sampled challenges must fail the

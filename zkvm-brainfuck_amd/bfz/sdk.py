@@ -1856,6 +1856,13 @@ def set_num_queries(q: int) -> None:
     check(lib().bfz_set_num_queries(int(q)))
 
 
+def set_air_max_degree(degree: int) -> None:
+    """The largest constraint degree air_info / air_check / air_prove / air_verify accept: 3..9,
+    0 = the default (3).  Degrees 4 and 5 prove with 4 quotient chunks, 6 to 9 with 8.  Chip
+    programs and machines keep their own limit of 3."""
+    check(lib().bfz_set_air_max_degree(int(degree)))
+
+
 def set_pcs_variant(observe_openings: int) -> None:
     """Decision D1: 1 = opened values observed before FRI alpha (default),
     0 = alpha sampled first, -1 = environment BFZ_OBSERVE_OPENINGS."""

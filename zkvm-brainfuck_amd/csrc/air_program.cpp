@@ -3,6 +3,7 @@
 #include "air_program.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -27,7 +28,38 @@ constexpr int DEG_CAP = 1 << 20;  // a product chain must not overflow the degre
 struct Node {
   uint32_t op, a, b;
 };
+std::atomic<int> g_max_degree{AIR_DEFAULT_MAX_DEGREE};
 }  // namespace
+
+int air_max_degree() { return g_max_degree.load(std::memory_order_relaxed); }
+
+void set_air_max_degree(int degree) {
+  if (degree != 0 && (degree < AIR_DEFAULT_MAX_DEGREE || degree > AIR_TOP_MAX_DEGREE))
+    throw std::runtime_error("air max degree must be in [3, 9] (0 = the default, 3)");
+  g_max_degree.store(degree ? degree : AIR_DEFAULT_MAX_DEGREE, std::memory_order_relaxed);
+}
+
+void air_degree_throw() {
+  throw std::runtime_error("uni_stark: constraint degree above " + std::to_string(air_max_degree()) +
+                           " is not supported");
+}
+
+// Z_H(x) = x^n - 1 at x = 3 g^r w_2n^i: g^n = w_D, w_2n^n = -1.
+SlabParams slab_params(size_t n, int lqd, int r, const kb::EF* alpha_pows) {
+  using namespace kb;
+  const int logn = log2i(n);
+  const uint32_t g = two_adic_gen(logn + lqd);
+  const uint32_t sn = mmul(mpow(to_mont(3), n), mpow(mpow(g, n), (uint64_t)r));
+  SlabParams sp{};
+  sp.alpha_pows = alpha_pows;
+  sp.shift = mmul(to_mont(3), mpow(g, (uint64_t)r));
+  sp.zh_even = msub(sn, ONE);
+  sp.zh_odd = msub(mneg(sn), ONE);
+  sp.zh_even_inv = minv(sp.zh_even);
+  sp.zh_odd_inv = minv(sp.zh_odd);
+  sp.wn_inv = minv(two_adic_gen(logn));
+  return sp;
+}
 
 AirProgram air_compile(const uint8_t* prog, size_t len) {
   if (!prog || len < 16) bad("shorter than its header", 0);
@@ -92,7 +124,7 @@ AirProgram air_compile(const uint8_t* prog, size_t len) {
   }
   int lqd = 0;  // log2_ceil(degree - 1), at least 0 (uni_air_shape)
   while ((1 << lqd) < degree - 1) lqd++;
-  if (lqd > 1) throw std::runtime_error("uni_stark: constraint degree above 3 is not supported");
+  if (degree > air_max_degree()) air_degree_throw();
 
   // ---- compile.  uses[i]: reads of node i by reachable nodes and by constraints still ahead.
   std::vector<uint32_t> uses(nn, 0);

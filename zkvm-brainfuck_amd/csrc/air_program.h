@@ -44,8 +44,17 @@ struct AirProgram {
   int instructions = 0;        // of the list (a CONST counts once)
 };
 
-// Throws std::runtime_error: a malformed program, a degree above 3 (uni_dims_or_throw's message),
-// more than BFZ_AIR_MAX_LIVE live values.  Reads nothing outside [prog, prog + len).
+// The largest constraint degree the AIR-program path accepts (bfz_set_air_max_degree): 3 unless
+// raised, 9 at most (8 quotient chunks).  Process-wide; chip_compile keeps its own limit of 3.
+constexpr int AIR_DEFAULT_MAX_DEGREE = 3, AIR_TOP_MAX_DEGREE = 9;
+int air_max_degree();
+void set_air_max_degree(int degree);  // 0 = the default; throws outside {0, 3..9}
+// uni_dims_or_throw's message for a degree above the cap in force.
+[[noreturn]] void air_degree_throw();
+
+// Throws std::runtime_error: a malformed program, a degree above air_max_degree()
+// (uni_dims_or_throw's message), more than BFZ_AIR_MAX_LIVE live values.  Reads nothing outside
+// [prog, prog + len).
 AirProgram air_compile(const uint8_t* prog, size_t len);
 
 // The BFA1 bytes of a built-in chip's AIR; refuses the chips uni_air_shape_or_throw refuses.
@@ -94,6 +103,21 @@ struct QuotOut;
 void launch_quotient_prog(int lqd, const uint32_t* code_dev, int ncode, const uint32_t* mainc,
                           int logN, const QuotParams* qp_dev, const uint32_t* twf,
                           const uint32_t* sel_inv, const QuotOut& qo, hipStream_t st);
+// One coset slab of the quotient of an AIR of degree above 3 (k_quotient_prog_coset): slab r of
+// the quotient domain 3 H_(D n), D = 2^lqd, is S_r = 3 g^r H_2n with g = w_(D n).  slab = the
+// trace's LDE on S_r (coset_lde with shift 3 g^r: column-major, 2^logN rows); natural point i of
+// the slab is quotient point r + i D/2, so the even i are chunk r and the odd i chunk r + D/2.
+struct SlabParams {
+  const kb::EF* alpha_pows;  // device array: alpha^(K-1-k), as QuotParams'
+  uint32_t shift;            // 3 g^r
+  uint32_t zh_even, zh_odd, zh_even_inv, zh_odd_inv;  // Z_H = 3^n w_D^r (+-1) - 1 at even / odd i
+  uint32_t wn_inv;           // w_n^-1
+};
+SlabParams slab_params(size_t n, int lqd, int r, const kb::EF* alpha_pows);
+// qo.chunk[0] / [1]: where chunk r / r + D/2 go (n values each, bit-reversed chunk order).
+void launch_quotient_prog_coset(const uint32_t* code_dev, int ncode, const uint32_t* slab, int logN,
+                                const SlabParams* sp_dev, const uint32_t* twf, const QuotOut& qo,
+                                hipStream_t st);
 // The row check of a column-major bit-reversed trace of h rows: res = {min(row * K + index) or ~0,
 // failing rows}; per_row_dev (optional) by storage position.
 void launch_check_prog(const uint32_t* code_dev, int ncode, const uint32_t* mainc, size_t h, int K,

@@ -1,6 +1,8 @@
 // Constraint programs on the device (air_program.h): one interpreter, run_program<Sink>, and the
 // two kernels around it -- k_quotient_prog<LQD> with the frame of k_quotient_air<CHIP, LQD>
-// (quotient.hip) and k_check_prog with the frame of k_check_air<CHIP> (debug_check.hip).
+// (quotient.hip) and k_check_prog with the frame of k_check_air<CHIP> (debug_check.hip) -- and
+// k_quotient_prog_coset, the quotient frame on a coset slab of the larger quotient domain an AIR
+// of degree 4 to 9 needs (uni_stark.hip quotient_slabs).
 //
 // The compiled list is wave-uniform: it is read through the constant address space (as PowAcc
 // reads the alpha powers), so the reads are scalar loads, and decoded with a switch.  The values
@@ -51,6 +53,81 @@ __global__ __launch_bounds__(256) void k_quotient_prog(const uint32_t* __restric
   const size_t chunk = LQD ? t >> (logN - 1) : 0, pos = t & (n - 1);
 #pragma unroll
   for (int e = 0; e < 4; e++) qo.chunk[chunk][e * qo.stride + pos] = q.c[e];
+}
+
+// 1 / d for the block's 256 values d (none zero) with one field inversion: an inclusive prefix
+// and an inclusive suffix product inside each wave by shuffles (6 steps each), the four wave
+// totals through LDS, one minv of the block's product by thread 0, and
+//   1 / d_i = (product before i) (product after i) / (product of all).
+// Every thread of the block calls it (two barriers).
+__device__ __forceinline__ uint32_t block_inverse(uint32_t d, uint32_t* s_wave, uint32_t* s_tinv) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t pre = d, suf = d;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t up = __shfl_up(pre, off, 64), dn = __shfl_down(suf, off, 64);
+    if (lane >= (uint32_t)off) pre = mmul(pre, up);
+    if (lane + off < 64) suf = mmul(suf, dn);
+  }
+  if (lane == 63) s_wave[wave] = pre;  // the wave's product
+  __syncthreads();
+  if (threadIdx.x == 0)
+    *s_tinv = minv(mmul(mmul(s_wave[0], s_wave[1]), mmul(s_wave[2], s_wave[3])));
+  // the product before / after the thread's own value: inside the wave, then the other waves
+  uint32_t before = __shfl_up(pre, 1, 64), after = __shfl_down(suf, 1, 64);
+  if (lane == 0) before = ONE;
+  if (lane == 63) after = ONE;
+#pragma unroll
+  for (uint32_t k = 0; k < 4; k++) {
+    const uint32_t wk = s_wave[k];
+    if (k < wave) before = mmul(before, wk);
+    if (k > wave) after = mmul(after, wk);
+  }
+  __syncthreads();
+  return mmul(mmul(before, after), *s_tinv);
+}
+
+// k_quotient_prog<1> on a coset slab S_r = 3 g^r H_2n, r >= 1, of the quotient domain 3 H_(D n)
+// (air_program.h SlabParams): one thread per slab point, the slot file and the scalar list as
+// above, the trace's next row at i + 2.  What differs from the frame on 3 H_2n: the point is
+// sp.shift w_2n^i, Z_H takes the slab's two values, and the selector denominators
+// (x - 1)(x - w_n^-1), which quotient_sel_inv tabulates for 3 H_N alone, are inverted here, one
+// inversion per block (block_inverse; a slab is disjoint from H_n, so none is zero).  A thread past
+// the slab (n = 1 .. 64: a partial block) brings the denominator 1 and stops after the barriers.
+// LDS: 32 KiB of slots + 20 bytes, the occupancy of k_quotient_prog.
+__global__ __launch_bounds__(256) void k_quotient_prog_coset(const uint32_t* __restrict__ code,
+                                                             int ncode,
+                                                             const uint32_t* __restrict__ slab,
+                                                             int logN,
+                                                             const SlabParams* __restrict__ spp,
+                                                             const uint32_t* __restrict__ twf,
+                                                             QuotOut qo) {
+  __shared__ uint32_t slots[BFZ_AIR_MAX_LIVE][256];
+  __shared__ uint32_t s_wave[4], s_tinv;
+  const SlabParams sp = *spp;
+  const size_t N = (size_t)1 << logN, n = N >> 1;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool has_point = t < N;
+  const uint32_t i = dbitrev(has_point ? (uint32_t)t : 0u, logN);  // in bounds whatever t
+  const uint32_t x = quot_point(i, (uint32_t)n, sp.shift, twf);
+  const uint32_t a = msub(x, ONE), b = msub(x, sp.wn_inv);
+  const uint32_t inv_ab = block_inverse(has_point ? mmul(a, b) : ONE, s_wave, &s_tinv);
+  if (!has_point) return;  // (no barrier below)
+
+  const uint32_t inext = (i + 2) & (uint32_t)(N - 1);
+  const uint32_t vt = (uint32_t)t * 4u, vn = dbitrev(inext, logN) * 4u;
+  const uint32_t zh = (i & 1) ? sp.zh_odd : sp.zh_even;
+  const uint32_t zh_inv = (i & 1) ? sp.zh_odd_inv : sp.zh_even_inv;
+  const uint32_t zi = mmul(zh, inv_ab);
+  const uint32_t is_first = mmul(zi, b), is_last = mmul(zi, a), is_trans = b;
+
+  PowAcc acc{{0, 0, 0, 0}, 0, (ConstWords)sp.alpha_pows, 0};
+  run_program((ConstWords)code, ncode, slots, slab, N, vt, vn, is_first, is_last, is_trans, acc);
+  const EF q = ef_mul_base(acc.value(), zh_inv);
+  // even i (t < n): chunk r, odd i: chunk r + D/2; position bitrev(i >> 1) = t mod n
+  const size_t half = t >> (logN - 1), pos = t & (n - 1);
+#pragma unroll
+  for (int e = 0; e < 4; e++) qo.chunk[half][e * qo.stride + pos] = q.c[e];
 }
 
 __global__ __launch_bounds__(256) void k_check_prog(const uint32_t* __restrict__ code, int ncode,
@@ -112,6 +189,16 @@ void launch_quotient_prog(int lqd, const uint32_t* code_dev, int ncode, const ui
   KCHECK();
 }
 
+void launch_quotient_prog_coset(const uint32_t* code_dev, int ncode, const uint32_t* slab, int logN,
+                                const SlabParams* sp_dev, const uint32_t* twf, const QuotOut& qo,
+                                hipStream_t st) {
+  if (logN < 1 || logN > 24) throw std::runtime_error("quotient_prog: bad LDE height");
+  const size_t count = (size_t)1 << logN;
+  hipLaunchKernelGGL(k_quotient_prog_coset, dim3(ceil_div(count, 256)), dim3(256), 0, st, code_dev,
+                     ncode, slab, logN, sp_dev, twf, qo);
+  KCHECK();
+}
+
 void launch_check_prog(const uint32_t* code_dev, int ncode, const uint32_t* mainc, size_t h, int K,
                        unsigned long long* res_dev, int32_t* per_row_dev, hipStream_t st) {
   hipLaunchKernelGGL(k_check_prog, dim3(ceil_div(h, 256)), dim3(256), 0, st, code_dev, ncode, mainc,
@@ -131,6 +218,7 @@ void launch_profile_prog(const uint32_t* code_dev, int ncode, const uint32_t* ma
 // kernels a proof or a check of a program launches (gpu.h PreloadKernels)
 static PreloadKernels preload_air_program{(const void*)&k_quotient_prog<0>,
                                           (const void*)&k_quotient_prog<1>,
+                                          (const void*)&k_quotient_prog_coset,
                                           (const void*)&k_check_prog,
                                           (const void*)&k_profile_prog};
 

@@ -2680,6 +2680,13 @@ int bfz_set_num_queries(int q) {
   });
 }
 
+int bfz_set_air_max_degree(int degree) {
+  return guarded([&] {
+    bfz::set_air_max_degree(degree);
+    return 0;
+  });
+}
+
 int bfz_coset_lde(const uint32_t* evals, size_t n, size_t w, uint32_t shift, uint32_t* out) {
   return guarded([&] {
     if (n == 0 || (n & (n - 1))) throw std::runtime_error("height must be a power of two");

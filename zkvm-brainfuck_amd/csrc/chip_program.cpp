@@ -25,8 +25,8 @@ ChipProgram chip_compile(const uint8_t* air, size_t air_len, const uint8_t* look
   p.lk = lookups_compile(lookups, lookups_len);
   p.has_air = air != nullptr && air_len != 0;
   if (p.has_air) {
-    p.air = air_compile(air, air_len);  // (refuses a degree above 3 itself)
-    if (p.air.degree > 3)
+    p.air = air_compile(air, air_len);  // (refuses a degree above air_max_degree() itself)
+    if (p.air.degree > 3)  // whatever that cap: a chip's quotient has two chunks
       throw std::runtime_error("chip program: AIR degree " + std::to_string(p.air.degree) +
                                " is above 3 (log quotient degree 1)");
     if (p.air.width != p.lk.main_w)

@@ -79,6 +79,12 @@ void quotient_air(int chip, int lqd, const uint32_t* mainc, int logN, const Quot
 void quotient_prog(const uint32_t* code_dev, int ncode, int lqd, const uint32_t* mainc, int logN,
                    const QuotParams& qp, const QuotParams* qp_dev, const QuotOut& out,
                    hipStream_t st);
+// A program of degree above 3 (log quotient degree 2 or 3): the quotient of one coset slab
+// S_r = 3 g^r H_2n, r >= 1, of 3 H_(D n) from the trace's LDE on that slab; slab 0 is the
+// committed LDE and goes through quotient_prog with lqd = 1 (air_program.h SlabParams).
+struct SlabParams;
+void quotient_prog_coset(const uint32_t* code_dev, int ncode, const uint32_t* slab, int logN,
+                         const SlabParams* sp_dev, const QuotOut& out, hipStream_t st);
 // Constraints Air::eval_air<chip> emits, their maximal degree and log2_ceil(degree - 1)
 // (chip.rs:82-87), computed from air.h.  false: the chip has no AIR constraints of its own.
 bool uni_air_shape(int chip, int* num_constraints, int* degree, int* log_quotient_degree);

@@ -280,6 +280,17 @@ void quotient_prog(const uint32_t* code_dev, int ncode, int lqd, const uint32_t*
                        sel, qout, st);
 }
 
+// One coset slab of a program's quotient on 3 H_(D n), D = 4 or 8 (air_program.h SlabParams):
+// k_quotient_prog_coset, which needs the twiddles alone -- it inverts its selector denominators
+// itself, so no table is built per slab and per height.
+void quotient_prog_coset(const uint32_t* code_dev, int ncode, const uint32_t* slab, int logN,
+                         const SlabParams* sp_dev, const QuotOut& qout, hipStream_t st) {
+  if (logN < 1 || logN > 24) throw std::runtime_error("quotient_prog: bad LDE height");
+  twiddles().ensure(logN);
+  launch_quotient_prog_coset(code_dev, ncode, slab, logN, sp_dev,
+                             (const uint32_t*)twiddles().fwd(), qout, st);
+}
+
 // The machine quotient of a chip that arrives as a pair of programs (chip_program.h): the same
 // tables, k_quotient_chip_prog<has AIR> instead of k_quotient<CHIP>.
 void quotient_chip_prog(const ChipLists& cl, const uint32_t* mainc, const uint32_t* prepc,

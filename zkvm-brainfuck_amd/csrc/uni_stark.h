@@ -55,7 +55,8 @@ std::vector<uint8_t> uni_prove_evals(int chip, const uint32_t* evals, size_t n, 
                                      const UniOptions& opt, StageTimes* times);
 
 // The input checks every uni-STARK call shares, with uni_prove's messages: the chip
-// (uni_air_shape_or_throw), a constraint degree above 3, the width, the height.
+// (uni_air_shape_or_throw), a constraint degree above air_max_degree() (3 unless raised), the
+// width, the height (at most 2^(24 - lqd) from lqd 2: the quotient domain must exist).
 void uni_dims_or_throw(int chip, size_t height, size_t width);
 void uni_dims_or_throw(const UniAir& air, size_t height, size_t width);
 [[noreturn]] void uni_noncanonical_throw(const char* name);  // a trace word >= p

@@ -4,7 +4,9 @@
 //   trace commit        commit_lde + Round::commit            (Pcs::commit, one matrix on H_n)
 //   transcript head     observe F(log n), the trace commitment, no public values
 //                       (utils/prove.rs:111), alpha = sample_ext_element          (U1, U2)
-//   quotient            k_quotient_air on 3 H_(n 2^lqd), chunks committed as one round  (U3, U4)
+//   quotient            k_quotient_air on 3 H_(n 2^lqd), chunks committed as one round  (U3, U4);
+//                       a program of degree 4 to 9 (lqd 2, 3): coset slab by coset slab,
+//                       quotient_slabs below
 //   PCS open            [trace: (zeta, zeta w_n)], [chunk j: (zeta)]: pcs_open (pcs_open.hip), the
 //                       machine prover's opening, on the unsharded plan with the two rounds in
 //                       one opening group (D1-D11)                                      (U5)
@@ -88,13 +90,17 @@ UniAir uni_air_of_program(const AirProgram& p) {
 }
 
 void uni_dims_or_throw(const UniAir& air, size_t height, size_t width) {
-  if (air.log_quotient_degree > 1)
-    throw std::runtime_error("uni_stark: constraint degree above 3 is not supported");
+  if (air.degree > air_max_degree()) air_degree_throw();
   if ((size_t)air.width != width)
     throw std::runtime_error(std::string("uni_stark: width mismatch for ") + air.name);
   if (height < 1 || (height & (height - 1)) || height > ((size_t)1 << 23))
     throw std::runtime_error(std::string("uni_stark: height not a power of two in [1, 2^23] for ") +
                              air.name);
+  // the quotient domain 3 H_(n 2^lqd) must exist: KoalaBear's two-adicity is 24
+  if (air.log_quotient_degree > 1 && height > ((size_t)1 << (24 - air.log_quotient_degree)))
+    throw std::runtime_error("uni_stark: height above 2^" +
+                             std::to_string(24 - air.log_quotient_degree) + " at constraint degree " +
+                             std::to_string(air.degree) + " for " + air.name);
 }
 
 void uni_dims_or_throw(int chip, size_t height, size_t width) {
@@ -148,6 +154,50 @@ std::vector<uint8_t> uni_prove_evals(int chip, const uint32_t* evals, size_t n, 
 }
 
 namespace {
+// The quotient of a program of degree above 3: D = 2^lqd = 4 or 8 chunks on 3 H_(D n), a domain
+// larger than the committed LDE.  With g = w_(D n) it is the union of the D/2 slabs
+// S_r = 3 g^r H_2n; natural point i of slab r is quotient point r + i D/2, so the slab's even
+// points are chunk r (on 3 g^r H_n) and its odd points chunk r + D/2, both in the bit-reversed
+// order the chunk's LDE takes, and the trace's next row is i + 2 -- the geometry of 3 H_2n.
+//   slab 0      the committed trace LDE through k_quotient_prog<1> as it is (the cached selector
+//               table of 3 H_2n); chunks 0 and D/2 land in their own half of their LDE and the
+//               other half is one half-transform, as at lqd = 1;
+//   slab r >= 1 the trace's LDE on S_r into ONE scratch buffer reused by every slab (the extra
+//               memory is one LDE, not D/2), k_quotient_prog_coset over it into a 2 x 4 x n
+//               value buffer, then the two chunks' full LDEs (shift 3 / (3 g^j) = g^-j).
+// One launch per slab, all on the proof's stream, which orders the reuse of the two buffers.
+void quotient_slabs(const AirProgram& prog, const uint32_t* evals, size_t n, const CMat& trace,
+                    const EF* apows_d, const QuotParams& qp, const QuotParams* qp_d, Round& quotr,
+                    hipStream_t st) {
+  const int lqd = prog.log_quotient_degree, w = prog.width, half = 1 << (lqd - 1);
+  const int logN = log2i(n) + LOG_BLOWUP;
+  const size_t N = 2 * n;
+  const uint32_t g_inv = minv(two_adic_gen(log2i(n) + lqd));
+  DBuf<uint32_t> code_d(prog.code.size());  // (stream-ordered: freed after the launches is fine)
+  upload_async(code_d.p, prog.code.data(), prog.code.size() * 4, st);
+  const int ncode = (int)prog.code.size();
+
+  CMat &q0 = quotr.mats[0], &qh = quotr.mats[half];
+  quotient_prog(code_d.p, ncode, 1, trace.lde.buf.p, logN, qp, qp_d,
+                QuotOut{{q0.lde.buf.p, qh.lde.buf.p + n}, N}, st);
+  coset_lde_ex(q0.lde.buf.p, N, n, 4, ONE, q0.lde.buf.p, 1, st);
+  coset_lde_ex(qh.lde.buf.p + n, N, n, 4, mpow(g_inv, (uint64_t)half), qh.lde.buf.p, 0, st);
+
+  std::vector<SlabParams> sp((size_t)half - 1);
+  for (int r = 1; r < half; r++) sp[r - 1] = slab_params(n, lqd, r, apows_d);
+  DBuf<SlabParams> sp_d(sp.size());
+  upload_async(sp_d.p, sp.data(), sp.size() * sizeof(SlabParams), st);
+  DBuf<uint32_t> slab(N * (size_t)w), vals(8 * n);
+  for (int r = 1; r < half; r++) {
+    coset_lde(evals, n, w, sp[r - 1].shift, slab.p, st);
+    quotient_prog_coset(code_d.p, ncode, slab.p, logN, sp_d.p + (r - 1),
+                        QuotOut{{vals.p, vals.p + 4 * n}, n}, st);
+    coset_lde(vals.p, n, 4, mpow(g_inv, (uint64_t)r), quotr.mats[r].lde.buf.p, st);
+    coset_lde(vals.p + 4 * n, n, 4, mpow(g_inv, (uint64_t)(r + half)),
+              quotr.mats[r + half].lde.buf.p, st);
+  }
+}
+
 // The prover from device evaluations (evals, n) in the library layout (column-major,
 // bit-reversed): everything after the fronts.  The inputs have been checked.
 std::vector<uint8_t> prove_core(const UniAir& air, const uint32_t* evals, size_t n,
@@ -196,7 +246,7 @@ std::vector<uint8_t> prove_core(const UniAir& air, const uint32_t* evals, size_t
     CMat& qm = quotr.mats[j];
     qm.n = n;
     qm.log_n = logn;
-    qm.shift = mmul(three, j ? wq : ONE);
+    qm.shift = mmul(three, mpow(wq, (uint64_t)j));
     qm.lde.height = N;
     qm.lde.width = 4;
     qm.lde.buf.reset(4 * N);
@@ -205,7 +255,9 @@ std::vector<uint8_t> prove_core(const UniAir& air, const uint32_t* evals, size_t
     qm.row0 = 0;
     for (int c = 0; c < 64; c++) qm.nmap[c] = (uint8_t)c;
   }
-  {
+  if (lqd > 1) {
+    quotient_slabs(*air.prog, evals, n, tracer.mats[0], apows_d.p, qp, qp_d.p, quotr, st);
+  } else {
     QuotOut qo{};
     qo.chunk[0] = quotr.mats[0].lde.buf.p;
     qo.chunk[1] = nchunks > 1 ? quotr.mats[1].lde.buf.p + n : nullptr;
@@ -219,7 +271,7 @@ std::vector<uint8_t> prove_core(const UniAir& air, const uint32_t* evals, size_t
       quotient_air(air.chip, lqd, tracer.mats[0].lde.buf.p, Lmax, qp, qp_d.p, qo, st);
     }
   }
-  for (int j = 0; j < nchunks; j++) {  // the other half of each chunk's LDE on 3 H_2n
+  for (int j = 0; j < nchunks && lqd <= 1; j++) {  // the other half of each chunk's LDE on 3 H_2n
     CMat& qm = quotr.mats[j];
     const uint32_t lde_shift = mmul(three, minv(qm.shift));  // GENERATOR / shift
     coset_lde_ex(qm.lde.buf.p + (size_t)j * n, N, n, 4, lde_shift, qm.lde.buf.p, 1 - j, st);

@@ -1031,13 +1031,16 @@ struct UniState {
 void uni_before_queries(const UniAir& air, Challenger& ch, const uint8_t* proof, size_t len,
                         const UniOptions& opt, UniState& U) {
   const int lqd = air.log_quotient_degree;
-  if (lqd > 1) throw std::runtime_error("chip has no uni-STARK AIR");
+  // 2^lqd chunks; above 1 for a program alone (air_compile's degree cap: 8 chunks at most)
+  if (lqd > (air.prog ? 3 : 1)) throw std::runtime_error("chip has no uni-STARK AIR");
   U.u = decode_bfu1(proof, len);
   const UniProof& u = U.u;
   // a program's proof: the chip word is a label outside the transcript and is not interpreted
   if (!air.prog && u.chip != (uint32_t)air.chip) throw std::runtime_error("proof is for another chip");
-  // unsigned: a huge word must not become a negative shift count below
-  if (u.log_degree > 23) throw std::runtime_error("log degree out of range");
+  // unsigned: a huge word must not become a negative shift count below; from 4 chunks the
+  // quotient domain 3 H_(n 2^lqd) must exist (two-adicity 24)
+  if (u.log_degree > 23 || (lqd > 1 && u.log_degree + (uint32_t)lqd > 24))
+    throw std::runtime_error("log degree out of range");
   const int log_n = U.log_n = (int)u.log_degree, nchunks = U.nchunks = 1 << lqd;
   U.air = air;
   const size_t w = (size_t)air.width;
