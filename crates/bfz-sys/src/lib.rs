@@ -213,6 +213,17 @@ pub struct bfz_chip_check {
     pub num_batches: i32,
     pub cumulative_sum: [u32; 4],
 }
+/// `bfz_machine_check`'s outcome for a machine of caller-defined chips: `ok == 1` needs every row
+/// of every chip to hold and `cumulative_sum` to be zero.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct bfz_machine_check_report {
+    pub ok: i32,
+    pub n_chips: i32,
+    pub alpha: [u32; 4],
+    pub beta: [u32; 4],
+    pub cumulative_sum: [u32; 4],
+}
 /// `StarkMachine::debug_constraints` (machine.rs:288-387) as plain data; `ok == 0` stands where
 /// the reference exits or panics.
 #[repr(C)]
@@ -631,6 +642,12 @@ extern "C" {
     pub fn bfz_machine_time(m: *const bfz_machine, chips: *const c_int, traces: *const *const u32,
                             heights: *const usize, n: usize, runs: c_int, perm_ms: *mut f32,
                             quot_ms: *mut f32) -> c_int;
+    /// `StarkMachine::debug_constraints` for the machine; `counts` / `first_rows` both or neither.
+    pub fn bfz_machine_check(m: *const bfz_machine, chips: *const c_int, traces: *const *const u32,
+                             heights: *const usize, n: usize, ch: *mut bfz_challenger,
+                             on_device: c_int, report: *mut bfz_machine_check_report,
+                             per_chip: *mut bfz_chip_check, counts: *mut u64,
+                             first_rows: *mut i64) -> c_int;
 
     pub fn bfz_set_num_queries(num_queries: c_int) -> c_int;
     pub fn bfz_set_pcs_variant(observe_openings: c_int) -> c_int;

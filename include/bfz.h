@@ -988,9 +988,39 @@ int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const u
  *                        launch over every chip) against the loop of per-chip launches
  *                        (k_perm_rows_prog, k_quotient_chip_prog) on the same device inputs,
  *                        alternating after one warm-up of each, whose words are compared.
- *                        perm_ms / quot_ms: 2 * runs floats, the segmented form's then the loop's. */
+ *                        perm_ms / quot_ms: 2 * runs floats, the segmented form's then the loop's.
+ *   bfz_machine_check    StarkMachine::debug_constraints (crates/stark/src/machine.rs:288-387) for
+ *                        the machine, the call to run before any proof: alpha then beta are
+ *                        sampled from ch (two sample_ext_element; ch is advanced, as in
+ *                        bfz_record_debug_constraints), every chip's permutation trace and
+ *                        cumulative sum are generated, and every constraint of every row of every
+ *                        included chip is evaluated on the trace domain.  chips / traces /
+ *                        heights / n as bfz_machine_prove, refused with its messages -- except
+ *                        that any number of chips may share a height (no tree is built) and that
+ *                        a machine made with with_traces = 0 is refused: it holds no preprocessed
+ *                        traces.  No LDE, no commit.  on_device = 1: the traces are uploaded
+ *                        once, and one launch per class of chips (with an AIR, lookup-only)
+ *                        checks all of them (k_check_machine, csrc/machine_program.hip); no
+ *                        permutation trace crosses the bus.  on_device = 0: a single-threaded
+ *                        loop over the same compiled lists.  Both give the same words.
+ *                        per_chip: n entries in the caller's order, chip = the index in creation
+ *                        order, the other fields as bfz_chip_check_rows reports them.  counts /
+ *                        first_rows (both or neither): sum of the chips' num_constraints entries,
+ *                        chip i's block at the sum of the earlier chips' num_constraints, with
+ *                        bfz_air_check_constraints' meaning -- the rows on which constraint k is
+ *                        not zero and the smallest of them in natural order, or -1;
+ *                        first_constraint is the smallest k whose first row is first_row.
+ *                        report->ok needs every row to hold AND the total cumulative sum to be
+ *                        zero; when the sum is not zero, bfz_lookups_debug over the same chips
+ *                        names the keys that do not balance.  Returns 0 whenever the check ran. */
 #define BFZ_MACHINE_MAX_CHIPS 32
 typedef struct bfz_machine bfz_machine;
+typedef struct {
+  int32_t ok;                 /* 1: every row of every chip holds AND cumulative_sum is zero */
+  int32_t n_chips;            /* = n */
+  uint32_t alpha[4], beta[4]; /* sampled from ch */
+  uint32_t cumulative_sum[4]; /* sum of the chips' cumulative sums (machine.rs:337) */
+} bfz_machine_check_report;
 int bfz_machine_create(const uint8_t* const* names, const size_t* name_lens,
                        const uint8_t* const* airs, const size_t* air_lens,
                        const uint8_t* const* lookups, const size_t* lookups_lens,
@@ -1012,6 +1042,10 @@ int bfz_machine_verify_time(const bfz_machine* m, bfz_challenger* chs,
                             float* ms);
 int bfz_machine_time(const bfz_machine* m, const int* chips, const uint32_t* const* traces,
                      const size_t* heights, size_t n, int runs, float* perm_ms, float* quot_ms);
+int bfz_machine_check(const bfz_machine* m, const int* chips, const uint32_t* const* traces,
+                      const size_t* heights, size_t n, bfz_challenger* ch, int on_device,
+                      bfz_machine_check_report* report, bfz_chip_check* per_chip,
+                      uint64_t* counts, int64_t* first_rows);
 
 /* FRI_QUERIES (kb31_poseidon2.rs:59-62): 1..4096, or 0 = environment FRI_QUERIES / 84. */
 int bfz_set_num_queries(int num_queries);

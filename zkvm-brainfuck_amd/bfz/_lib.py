@@ -61,6 +61,12 @@ class ChipCheck(ctypes.Structure):
                 ("num_batches", c_int32), ("cumulative_sum", c_uint32 * 4)]
 
 
+class MachineCheckReport(ctypes.Structure):
+    """bfz_machine_check_report: the machine-level outcome of bfz_machine_check."""
+    _fields_ = [("ok", c_int32), ("n_chips", c_int32), ("alpha", c_uint32 * 4),
+                ("beta", c_uint32 * 4), ("cumulative_sum", c_uint32 * 4)]
+
+
 class DebugReportC(ctypes.Structure):
     """bfz_debug_report: StarkMachine::debug_constraints' outcome as plain data."""
     _fields_ = [("ok", c_int32), ("n_chips", c_int32), ("balance_valid", c_int32), ("_pad", c_int32),
@@ -338,6 +344,10 @@ SIGNATURES = [
     ("bfz_machine_time", c_int, [c_void_p, POINTER(c_int), POINTER(POINTER(c_uint32)),
                                  POINTER(c_size_t), c_size_t, c_int, POINTER(ctypes.c_float),
                                  POINTER(ctypes.c_float)]),
+    ("bfz_machine_check", c_int, [c_void_p, POINTER(c_int), POINTER(POINTER(c_uint32)),
+                                  POINTER(c_size_t), c_size_t, POINTER(Challenger), c_int,
+                                  POINTER(MachineCheckReport), POINTER(ChipCheck),
+                                  POINTER(c_uint64), POINTER(c_int64)]),
     ("bfz_set_num_queries", c_int, [c_int]),
     ("bfz_set_pcs_variant", c_int, [c_int]),
     ("bfz_set_air_max_degree", c_int, [c_int]),

@@ -1687,6 +1687,30 @@ MACHINE_MAX_CHIPS = 32
 _CHECK_ALPHA, _CHECK_BETA = [_mont(5), _mont(7), _mont(11), _mont(13)], [_mont(2), _mont(3), 0, _mont(1)]
 
 
+@dataclass
+class MachineCheckReport:
+    """bfz_machine_check: what Machine.check found.  chips[j] / names[j] / counts[j] / first_rows[j]
+    belong to the j-th trace given; a chip's `chip` is its index in the machine's creation order."""
+    ok: bool
+    alpha: List[int]
+    beta: List[int]
+    cumulative_sum: List[int]  # the sum of the chips' cumulative sums; ok needs it to be zero
+    chips: List[ChipCheckResult]
+    names: List[str]
+    counts: Optional[list] = None      # per chip: numpy uint64[num_constraints] (profile=True)
+    first_rows: Optional[list] = None  # per chip: numpy int64[num_constraints], -1 = never fails
+
+    def __str__(self) -> str:
+        lines = [f"machine check: {'ok' if self.ok else 'FAILED'}; cumulative sum "
+                 f"{'zero' if not any(self.cumulative_sum) else 'NOT zero'}"]
+        for n, c in zip(self.names, self.chips):
+            lines.append(f"  {n:<12} {c.height:>8} rows, K = {c.num_constraints:<3} " + (
+                "ok" if not c.failing_rows else
+                f"FAILED: {c.failing_rows} failing row(s); first: row {c.first_row}, constraint "
+                f"{c.first_constraint}"))
+        return "\n".join(lines)
+
+
 class Machine:
     """A machine whose chips are data (bfz_machine_*).  chips: [(name, air or None, lookups,
     prep or None)], name str or bytes, prep the chip's preprocessed trace ((height, prep_width)
@@ -1790,6 +1814,36 @@ class Machine:
         _lib.check(lib().bfz_machine_prove(self._h, idx, ptrs, hs, k, ctypes.byref(ch),
                                            ctypes.byref(ptr), ctypes.byref(plen)))
         return take_bytes(ptr, plen.value)
+
+    def check(self, traces, ch: Optional[Challenger] = None, on_device: bool = True,
+              profile: bool = False) -> "MachineCheckReport":
+        """bfz_machine_check: StarkMachine::debug_constraints (crates/stark/src/machine.rs:288-387)
+        for this machine, the call to run before any proof.  traces as prove takes them; ch (None:
+        observe()) gives alpha then beta and is advanced.  Every constraint of every row of every
+        chip is evaluated and the chips' cumulative sums are added up: ok needs both every row to
+        hold and a zero total.  on_device=True checks all chips in one launch per class of chips;
+        False is a single-threaded host loop.  profile=True adds, per chip, counts[k] (the rows on
+        which constraint k is not zero) and first_rows[k] (the smallest of them, or -1).  When the
+        total is not zero, lookups_debug over the same chips names the keys that do not balance."""
+        import numpy as np
+        idx, ptrs, hs, k, items = self._traces_c(traces)
+        if ch is None:
+            ch = self.observe()
+        ks = [chip_info(*self.programs[i]).num_constraints for i, _ in items]
+        counts = np.zeros(sum(ks), dtype=np.uint64) if profile else None
+        firsts = np.zeros(sum(ks), dtype=np.int64) if profile else None
+        rep, per = _lib.MachineCheckReport(), (_lib.ChipCheck * max(k, 1))()
+        _lib.check(lib().bfz_machine_check(
+            self._h, idx, ptrs, hs, k, ctypes.byref(ch), int(bool(on_device)), ctypes.byref(rep), per,
+            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if profile else None,
+            firsts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if profile else None))
+        at = np.cumsum([0] + ks)
+        return MachineCheckReport(
+            ok=bool(rep.ok), alpha=list(rep.alpha), beta=list(rep.beta),
+            cumulative_sum=list(rep.cumulative_sum), chips=[_chip_result(per[j]) for j in range(k)],
+            names=[self.names[i].decode(errors="replace") for i, _ in items],
+            counts=[counts[at[j]:at[j + 1]] for j in range(k)] if profile else None,
+            first_rows=[firsts[at[j]:at[j + 1]] for j in range(k)] if profile else None)
 
     def verify(self, proof: bytes, ch: Challenger) -> VerifyOutcome:
         """bfz_machine_verify (host only): the outcome, with the verifier's reason; ch advanced."""

@@ -2180,6 +2180,36 @@ int bfz_machine_time(const bfz_machine* m, const int* chips, const uint32_t* con
   });
 }
 
+int bfz_machine_check(const bfz_machine* m, const int* chips, const uint32_t* const* traces,
+                      const size_t* heights, size_t n, bfz_challenger* ch, int on_device,
+                      bfz_machine_check_report* report, bfz_chip_check* per_chip, uint64_t* counts,
+                      int64_t* first_rows) {
+  return guarded([&] {
+    if (!m || !ch || !report || !per_chip) throw std::runtime_error("null argument");
+    if ((counts == nullptr) != (first_rows == nullptr))
+      throw std::runtime_error("machine_check: counts and first_rows are given together or not at all");
+    if (on_device && m->m->can_prove && g_bound < 0)
+      throw std::runtime_error("machine_check: no device bound (bfz_init) for on_device = 1");
+    bfz::Challenger c = from_c(ch);
+    const bfz::MachineCheck r =
+        bfz::machine_check(*m->m, chips, traces, heights, n, c, on_device != 0);
+    static_assert(sizeof(bfz_machine_check_report) == 56, "bfz_machine_check_report has no gaps");
+    std::memset(report, 0, sizeof *report);
+    report->ok = r.ok ? 1 : 0;
+    report->n_chips = (int32_t)n;
+    std::memcpy(report->alpha, r.alpha.c, 16);
+    std::memcpy(report->beta, r.beta.c, 16);
+    std::memcpy(report->cumulative_sum, r.cumsum.c, 16);
+    for (size_t i = 0; i < n; i++) to_c(r.chips[i], &per_chip[i]);
+    if (counts) {
+      std::memcpy(counts, r.counts.data(), r.counts.size() * sizeof(uint64_t));
+      std::memcpy(first_rows, r.first_rows.data(), r.first_rows.size() * sizeof(int64_t));
+    }
+    to_c(c, ch);  // advanced past the two samples
+    return 0;
+  });
+}
+
 int bfz_record_uni_check(const bfz_record* rec, int chip, bfz_uni_check_result* out) {
   return guarded([&] {
     if (!rec || !out) throw std::runtime_error("null argument");

@@ -2,6 +2,7 @@
 // single-threaded row check.
 #include "chip_program.h"
 
+#include <algorithm>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -50,21 +51,56 @@ EF ef_at(const uint32_t* w) {
   std::memcpy(e.c, w, 16);
   return e;
 }
+
+// The permutation constraints of one row into acc (batches + 3 emit_ext calls), in
+// perm_constraints' order.  m / pr: the row's main and preprocessed words; pl / pn: the local and
+// next permutation rows (4 * perm_width words each).
+template <class Acc>
+void host_perm_constraints(const ChipProgram& p, const uint32_t* m, const uint32_t* pr,
+                           const uint32_t* pl, const uint32_t* pn, const PermChallenges& ch,
+                           const EF& cumsum, bool is_first, bool is_last, Acc& acc) {
+  const uint32_t* list = p.lk.list.data();
+  const int nb = p.lk.batches(), ni = p.lk.n;
+  EF sum_l = ef_zero(), sum_n = ef_zero();
+  size_t at = LKP_HEAD;
+  for (int b = 0; b < nb; b++) {
+    EF d0, d1;
+    uint32_t m0, m1;
+    host_interaction(list, at, m, pr, ch, d0, m0);
+    const EF v = ef_at(pl + 4 * b);
+    if (2 * b + 1 < ni) {
+      host_interaction(list, at, m, pr, ch, d1, m1);
+      acc.emit_ext(ef_sub(ef_mul(ef_mul(d0, d1), v),
+                          ef_add(ef_mul_base(d1, m0), ef_mul_base(d0, m1))));
+    } else {
+      acc.emit_ext(ef_sub(ef_mul(d0, v), ef_base(m0)));
+    }
+    sum_l = ef_add(sum_l, v);
+    sum_n = ef_add(sum_n, ef_at(pn + 4 * b));
+  }
+  const EF phi_l = ef_at(pl + 4 * nb), phi_n = ef_at(pn + 4 * nb);
+  acc.emit_ext(is_first ? ef_sub(phi_l, sum_l) : ef_zero());
+  acc.emit_ext(is_last ? ef_zero() : ef_sub(ef_sub(phi_n, phi_l), sum_n));
+  acc.emit_ext(is_last ? ef_sub(phi_l, cumsum) : ef_zero());
+}
+
+void chip_dims_or_throw(const ChipProgram& p, const uint32_t* prep, size_t h) {
+  if (h < 1 || (h & (h - 1)) || h > ((size_t)1 << 23))
+    throw std::runtime_error("chip program: height not a power of two in [1, 2^23]");
+  if (p.lk.prep_w && !prep) throw std::runtime_error("chip program: the chip has preprocessed columns");
+}
 }  // namespace
 
 void chip_check_host(const ChipProgram& p, const uint32_t* main, const uint32_t* prep,
                      const uint32_t* perm, size_t h, const PermChallenges& ch, const EF& cumsum,
                      ChipCheck& out, int32_t* per_row) {
-  if (h < 1 || (h & (h - 1)) || h > ((size_t)1 << 23))
-    throw std::runtime_error("chip program: height not a power of two in [1, 2^23]");
-  if (p.lk.prep_w && !prep) throw std::runtime_error("chip program: the chip has preprocessed columns");
-  const int mw = p.lk.main_w, pw = p.lk.prep_w, nb = p.lk.batches(), ni = p.lk.n;
+  chip_dims_or_throw(p, prep, h);
+  const int mw = p.lk.main_w, pw = p.lk.prep_w;
   const size_t w = 4 * (size_t)p.perm_width();
-  const uint32_t* list = p.lk.list.data();
   out = ChipCheck{};
   out.height = h;
   out.num_constraints = p.num_constraints();
-  out.num_batches = nb;
+  out.num_batches = p.lk.batches();
   out.cumsum = cumsum;
   for (size_t i = 0; i < h; i++) {
     const size_t nx = (i + 1) & (h - 1);
@@ -72,36 +108,45 @@ void chip_check_host(const ChipProgram& p, const uint32_t* main, const uint32_t*
     const uint32_t* m = main + i * (size_t)mw;
     int idx = p.has_air ? air_first_fail(p.air, m, main + nx * (size_t)mw, is_first, is_last) : -1;
     if (idx < 0) {
-      const uint32_t* pr = pw ? prep + i * (size_t)pw : nullptr;
-      const uint32_t *pl = perm + i * w, *pn = perm + nx * w;
       HostFail acc{p.air_constraints()};
-      EF sum_l = ef_zero(), sum_n = ef_zero();
-      size_t at = LKP_HEAD;
-      for (int b = 0; b < nb; b++) {
-        EF d0, d1;
-        uint32_t m0, m1;
-        host_interaction(list, at, m, pr, ch, d0, m0);
-        const EF v = ef_at(pl + 4 * b);
-        if (2 * b + 1 < ni) {
-          host_interaction(list, at, m, pr, ch, d1, m1);
-          acc.emit_ext(ef_sub(ef_mul(ef_mul(d0, d1), v),
-                              ef_add(ef_mul_base(d1, m0), ef_mul_base(d0, m1))));
-        } else {
-          acc.emit_ext(ef_sub(ef_mul(d0, v), ef_base(m0)));
-        }
-        sum_l = ef_add(sum_l, v);
-        sum_n = ef_add(sum_n, ef_at(pn + 4 * b));
-      }
-      const EF phi_l = ef_at(pl + 4 * nb), phi_n = ef_at(pn + 4 * nb);
-      acc.emit_ext(is_first ? ef_sub(phi_l, sum_l) : ef_zero());
-      acc.emit_ext(is_last ? ef_zero() : ef_sub(ef_sub(phi_n, phi_l), sum_n));
-      acc.emit_ext(is_last ? ef_sub(phi_l, cumsum) : ef_zero());
+      host_perm_constraints(p, m, pw ? prep + i * (size_t)pw : nullptr, perm + i * w, perm + nx * w,
+                            ch, cumsum, is_first, is_last, acc);
       idx = acc.first;
     }
     if (per_row) per_row[i] = idx;
     if (idx >= 0 && out.failing_rows++ == 0) {
       out.first_row = (int64_t)i;
       out.first_constraint = idx;
+    }
+  }
+}
+
+void chip_profile_host(const ChipProgram& p, const uint32_t* main, const uint32_t* prep,
+                       const uint32_t* perm, size_t h, const PermChallenges& ch, const EF& cumsum,
+                       ChipCheck& out, uint64_t* counts, int64_t* first_rows) {
+  chip_dims_or_throw(p, prep, h);
+  const int mw = p.lk.main_w, pw = p.lk.prep_w, K = p.num_constraints();
+  const size_t w = 4 * (size_t)p.perm_width();
+  out = ChipCheck{};
+  out.height = h;
+  out.num_constraints = K;
+  out.num_batches = p.lk.batches();
+  out.cumsum = cumsum;
+  std::fill(counts, counts + K, (uint64_t)0);
+  std::fill(first_rows, first_rows + K, (int64_t)-1);
+  for (size_t i = 0; i < h; i++) {
+    const size_t nx = (i + 1) & (h - 1);
+    const bool is_first = i == 0, is_last = i == h - 1;
+    const uint32_t* m = main + i * (size_t)mw;
+    ProfileAcc acc{counts, first_rows, (int64_t)i};  // every constraint of the row, failed or not
+    if (p.has_air)
+      air_run<BaseOps>(p.air, m, main + nx * (size_t)mw, is_first ? ONE : 0u, is_last ? ONE : 0u,
+                       is_last ? 0u : ONE, acc);
+    host_perm_constraints(p, m, pw ? prep + i * (size_t)pw : nullptr, perm + i * w, perm + nx * w, ch,
+                          cumsum, is_first, is_last, acc);
+    if (acc.first >= 0 && out.failing_rows++ == 0) {
+      out.first_row = (int64_t)i;
+      out.first_constraint = acc.first;
     }
   }
 }

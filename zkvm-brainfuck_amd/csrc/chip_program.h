@@ -42,6 +42,12 @@ ChipProgram chip_compile(const uint8_t* air, size_t air_len, const uint8_t* look
 void chip_check_host(const ChipProgram& p, const uint32_t* main, const uint32_t* prep,
                      const uint32_t* perm, size_t h, const PermChallenges& ch, const kb::EF& cumsum,
                      ChipCheck& out, int32_t* per_row);
+// The same check with the constraint profile (ProfileAcc, as profile_air_host): every constraint
+// of every row is evaluated; counts[k] = the rows on which constraint k is not zero, first_rows[k]
+// = the smallest of them or -1 (K entries each); out is chip_check_host's summary.
+void chip_profile_host(const ChipProgram& p, const uint32_t* main, const uint32_t* prep,
+                       const uint32_t* perm, size_t h, const PermChallenges& ch, const kb::EF& cumsum,
+                       ChipCheck& out, uint64_t* counts, int64_t* first_rows);
 
 // ---- device side (chip_program.hip).  The lists in device memory; code is nullptr / ncode 0 for
 // a lookup-only chip (the kernels' HAS_AIR = 0 instantiation, which has no slot file).

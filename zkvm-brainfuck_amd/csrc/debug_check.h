@@ -99,6 +99,8 @@ struct ProfileAcc {
     n++;
     return true;  // (air_run: go on)
   }
+  // An EF emission (a chip's LogUp constraints) is not zero when any of its components is not.
+  KB_HD bool emit_ext(const EF& c) { return emit(c.c[0] | c.c[1] | c.c[2] | c.c[3]); }
 };
 
 // One row's interactions for the balance table (lookup/debug.rs:79-116): per LookupKind the sum
@@ -338,6 +340,7 @@ struct ProfileSink {
 #endif
     n++;
   }
+  KB_HD void emit_ext(const EF& c) { emit(c.c[0] | c.c[1] | c.c[2] | c.c[3]); }  // as FirstFailSink
 };
 
 // Block start: count = 0, first = none; ends with the barrier the emissions need.

@@ -7,6 +7,8 @@
 #include <set>
 #include <stdexcept>
 
+#include "uni_stark.h"
+
 namespace bfz {
 
 using namespace kb;
@@ -58,6 +60,10 @@ std::unique_ptr<MachineProgram> machine_create(const MachineChipIn* in, size_t n
   for (size_t k = 0; k < m->prep_chips.size(); k++) m->chips[m->prep_chips[k]].prep_index = (int)k;
   m->has_prep = !m->prep_chips.empty();
   if (with_traces) {
+    for (int i : m->prep_chips) {
+      const MachineChip& c = m->chips[i];
+      m->chips[i].prep_host.assign(in[i].prep, in[i].prep + c.prep_height * (size_t)c.p.lk.prep_w);
+    }
     machine_commit_prep(*m, in);
     m->can_prove = true;
   } else if (m->has_prep) {
@@ -72,6 +78,96 @@ std::unique_ptr<MachineProgram> machine_create(const MachineChipIn* in, size_t n
 void machine_observe(const MachineProgram& m, Challenger& ch) {
   ch.observe_digest(m.prep_root);  // eight zero words without preprocessed columns
   for (int i = 0; i < 7; i++) ch.observe(0);
+}
+
+std::vector<int> machine_trace_order(const MachineProgram& m, const int* chips,
+                                     const uint32_t* const* traces, const size_t* heights, size_t n,
+                                     bool same_height_limit) {
+  if (!chips || !traces || !heights || n == 0) throw std::runtime_error("machine: no traces");
+  if (n > m.chips.size()) throw std::runtime_error("machine: more traces than chips");
+  std::vector<bool> seen(m.chips.size(), false);
+  for (size_t i = 0; i < n; i++) {
+    const int c = chips[i];
+    if (c < 0 || (size_t)c >= m.chips.size() || seen[c])
+      throw std::runtime_error("machine: bad or repeated chip index");
+    seen[c] = true;
+    const MachineChip& ch = m.chips[c];
+    const size_t h = heights[i];
+    if (!traces[i]) throw std::runtime_error("machine: null trace for " + ch.name);
+    if (h < 1 || (h & (h - 1)) || h > ((size_t)1 << 23))
+      throw std::runtime_error("machine: height not a power of two in [1, 2^23] for " + ch.name);
+    if (ch.p.lk.prep_w && h != ch.prep_height)
+      throw std::runtime_error("machine: chip " + ch.name + " is not at its preprocessed height");
+  }
+  for (int pc : m.prep_chips)
+    if (!seen[pc])
+      throw std::runtime_error("machine: chip " + m.chips[pc].name +
+                               " has preprocessed columns and must be included");
+  if (same_height_limit)  // the machine prover's own limit (the commit has none, merkle.hip)
+    for (size_t i = 0; i < n; i++) {
+      size_t same = 0;
+      for (size_t j = 0; j < n; j++) same += heights[j] == heights[i];
+      if (same > MACHINE_MAX_SAME_HEIGHT)
+        throw std::runtime_error("machine: " + std::to_string(same) + " chips of height " +
+                                 std::to_string(heights[i]) + ", a proof takes at most " +
+                                 std::to_string(MACHINE_MAX_SAME_HEIGHT) + " of one height");
+    }
+  std::vector<int> order(n);
+  for (size_t i = 0; i < n; i++) order[i] = (int)i;
+  std::sort(order.begin(), order.end(), [&](int a, int b) {  // (Reverse(height), name)
+    if (heights[a] != heights[b]) return heights[a] > heights[b];
+    return m.chips[chips[a]].name < m.chips[chips[b]].name;
+  });
+  return order;
+}
+
+MachineCheck machine_check_device(const MachineProgram& m, const int* chips,
+                                  const uint32_t* const* traces, const size_t* heights, size_t n,
+                                  Challenger& ch);  // machine_program.hip
+
+MachineCheck machine_check(const MachineProgram& m, const int* chips, const uint32_t* const* traces,
+                           const size_t* heights, size_t n, Challenger& ch, bool on_device) {
+  if (!m.can_prove)
+    throw std::runtime_error("machine: a verifier-only machine holds no preprocessed traces and "
+                             "cannot check constraints");
+  if (on_device) return machine_check_device(m, chips, traces, heights, n, ch);
+  const std::vector<int> order = machine_trace_order(m, chips, traces, heights, n, false);
+  for (int i : order) {  // the device path's refusal, in its (commit) order
+    const MachineChip& c = m.chips[chips[i]];
+    for (size_t j = 0; j < heights[i] * (size_t)c.p.lk.main_w; j++)
+      if (traces[i][j] >= P) uni_noncanonical_throw(c.name.c_str());
+  }
+  MachineCheck out;
+  out.alpha = ch.sample_ef();  // machine.rs:300-303
+  out.beta = ch.sample_ef();
+  PermChallenges pch;
+  pch.alpha = out.alpha;
+  pch.beta_pows[0] = ef_one();
+  for (int j = 1; j < 8; j++) pch.beta_pows[j] = ef_mul(pch.beta_pows[j - 1], out.beta);
+  size_t ktot = 0;
+  for (size_t i = 0; i < n; i++) ktot += (size_t)m.chips[chips[i]].p.num_constraints();
+  out.chips.resize(n);
+  out.counts.resize(ktot);
+  out.first_rows.resize(ktot);
+  out.cumsum = ef_zero();
+  out.ok = true;
+  std::vector<uint32_t> perm;
+  size_t k0 = 0;
+  for (size_t i = 0; i < n; i++) {
+    const MachineChip& c = m.chips[chips[i]];
+    const uint32_t* prep = c.p.lk.prep_w ? c.prep_host.data() : nullptr;
+    perm.resize(heights[i] * 4 * (size_t)c.p.perm_width());
+    EF cs;
+    lookups_perm_trace_host(c.p.lk, traces[i], prep, heights[i], pch, perm.data(), &cs);
+    chip_profile_host(c.p, traces[i], prep, perm.data(), heights[i], pch, cs, out.chips[i],
+                      out.counts.data() + k0, out.first_rows.data() + k0);
+    out.chips[i].chip = chips[i];
+    out.cumsum = ef_add(out.cumsum, cs);
+    out.ok = out.ok && out.chips[i].failing_rows == 0;
+    k0 += (size_t)c.p.num_constraints();
+  }
+  out.ok = out.ok && ef_is_zero(out.cumsum);
+  return out;
 }
 
 namespace {

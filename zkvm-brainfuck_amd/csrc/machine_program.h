@@ -36,6 +36,7 @@ struct MachineChip {
   size_t prep_height = 0;
   DBuf<uint32_t> code, list;     // the device lists (a proving machine)
   DBuf<uint32_t> prep_evals;     // column-major bit-reversed preprocessed trace
+  std::vector<uint32_t> prep_host;  // the same trace as given (row-major): machine_check's host path
 };
 
 struct MachineProgram {
@@ -82,6 +83,32 @@ std::vector<VerifyOutcome> machine_verify_batch(const MachineProgram& m, Challen
                                                 const uint8_t* const* proofs, const size_t* lens,
                                                 size_t n, const VerifyOptions& opt,
                                                 QueryRunner run_queries);
+
+// machine_prove's refusals of its inputs (null or repeated chips, heights, a chip away from its
+// preprocessed height, a missing preprocessed chip; with same_height_limit the prover's
+// MACHINE_MAX_SAME_HEIGHT), then the commit order: positions in the caller's arrays sorted by
+// (Reverse(height), name).
+std::vector<int> machine_trace_order(const MachineProgram& m, const int* chips,
+                                     const uint32_t* const* traces, const size_t* heights, size_t n,
+                                     bool same_height_limit);
+
+// StarkMachine::debug_constraints (crates/stark/src/machine.rs:288-387) for the machine: alpha
+// then beta sampled from ch (advanced), every chip's permutation trace and cumulative sum, every
+// constraint of every row of every chip on the trace domain.  No LDE, no commit.  Inputs as
+// machine_prove's, refused as it refuses them, except that any number of chips may share a height.
+// on_device: k_perm_rows_machine, the running sums and k_check_machine<HAS_AIR> (one launch per
+// class of chips, every chip a segment); otherwise a single-threaded loop over the same compiled
+// lists that touches no device.  Both give the same words.
+struct MachineCheck {
+  bool ok = false;               // every row of every chip holds and cumsum is zero
+  EF alpha{}, beta{}, cumsum{};  // cumsum: the sum of the chips' cumulative sums (machine.rs:337)
+  std::vector<ChipCheck> chips;  // the caller's order; chip = the index in m.chips
+  // the constraint profile: chip i's num_constraints entries start at the sum of the earlier K
+  std::vector<uint64_t> counts;
+  std::vector<int64_t> first_rows;
+};
+MachineCheck machine_check(const MachineProgram& m, const int* chips, const uint32_t* const* traces,
+                           const size_t* heights, size_t n, Challenger& ch, bool on_device);
 
 // Diagnostic (bfz_machine_time): single launches of the segmented kernels (form A) against the
 // loop of per-chip launches (form B) on the same device inputs, alternating after one warm-up of

@@ -43,6 +43,13 @@
 //     that Cpu's 8-batch file allows.  Two classes at most: within the large class the tallest chip
 //     of the exported set is Cpu itself, and a third class would split launches that are already
 //     LDS-bound by their own chips.
+//   The constraint check (machine_check, k_check_machine<HAS_AIR>) is the third segmented launch:
+//     k_check_chip_prog's frame on the trace domain with ProfileSink through both phases, over the
+//     evaluations and the permutation rows where k_perm_rows_machine left them.  LDS: the 32 KiB
+//     slot file (HAS_AIR = 1) + reduce_failures' 48 bytes static, then 8 kmax bytes of dynamic
+//     count / first tables (kmax <= 531: 4248 bytes) -- 37064 bytes at most, 4 blocks (16 waves)
+//     per CU of 160 KiB, as k_check_chip_prog<1>; HAS_AIR = 0 declares the tables alone and is
+//     bounded by its 68 VGPRs (7 waves per SIMD).
 //   Running sums stay per chip (perm_running_sum): a scan's length is its chip's height.
 //   No scratch: the descriptor is read field by field from the constant address space, never
 //     copied into a private struct; private_segment_fixed_size is 0.
@@ -67,8 +74,10 @@ struct MachSeg {
   const uint32_t* sel_inv;                // quotient: the table of 3 H_N
   uint32_t* out[2];                       // quotient: QuotOut::chunk; permutation: out[0] = perm
   EF* rowsum;                             // permutation: the row sums
+  unsigned long long* res;                // check: {min key, failing rows, count[K], first[K]}
   size_t out_stride;                      // QuotOut::stride
-  uint32_t ncode, log_rows;               // log_rows: logN (quotient), log n (permutation)
+  uint32_t ncode, log_rows;               // log_rows: logN (quotient), log n (permutation, check)
+  uint32_t num_constraints, pad;          // check: K
   QuotParams qp;                          // begins with the LogUp challenges' words
 };
 struct MachTable {
@@ -188,6 +197,52 @@ __global__ __launch_bounds__(LKP_T) void k_perm_rows_machine(const MachTable* __
   T->seg[s].rowsum[t] = sum;
 }
 
+// k_check_chip_prog<HAS_AIR> for every segment of tab, with the constraint profile: one thread per
+// storage position t of a trace of n = 2^log_rows rows (evaluations, stride n), natural row i =
+// bitrev(t), next row (i + 1) mod n (n = 1: the row itself), selectors 0 / 1 words, is_transition =
+// 1 - is_last (debug.rs:43-94).  ProfileSink runs through run_program and perm_constraints, so one
+// pass gives the segment's summary (reduce_failures) and its count[K] / first[K] tables.
+// Dynamic LDS: kmax counts then kmax first rows, after the static slot file (HAS_AIR = 1) and
+// reduce_failures' 48 bytes.  kmax = the largest K of the launch; a segment uses a prefix.
+// A lane past its segment's last row evaluates row 0 of its OWN segment with row = PROFILE_NO_ROW:
+// every lane reaches every ballot, butterfly and barrier, no lane fails for a row that is not
+// there, and every load stays inside the segment's matrices (position 0 exists at any height).
+template <int HAS_AIR>
+__global__ __launch_bounds__(256) void k_check_machine(const MachTable* __restrict__ tab, int kmax) {
+  extern __shared__ uint32_t prof[];  // [2][kmax]
+  uint32_t(*slots)[256] = nullptr;
+  if constexpr (HAS_AIR) {
+    __shared__ uint32_t file[BFZ_AIR_MAX_LIVE][256];
+    slots = file;
+  }
+  uint32_t *s_cnt = prof, *s_fst = prof + kmax;
+  const ConstTable T = (ConstTable)tab;
+  const uint32_t s = find_segment(T);
+  const int K = (int)T->seg[s].num_constraints;  // <= kmax
+  profile_clear(s_cnt, s_fst, K);
+  const int logn = (int)T->seg[s].log_rows;
+  const uint32_t n = 1u << logn;
+  const uint32_t* mainc = T->seg[s].mainc;
+  const uint32_t t = (blockIdx.x - T->off[s]) * 256u + threadIdx.x;
+  const bool has_row = t < n;
+  const uint32_t ts = has_row ? t : 0u;  // in bounds of this segment whatever t
+  const uint32_t i = dbitrev(ts, logn);
+  const uint32_t vt = ts * 4u, vn = dbitrev((i + 1) & (n - 1), logn) * 4u;  // ts < n <= 2^23
+  const uint32_t first = i == 0 ? ONE : 0u, last = i == n - 1 ? ONE : 0u,
+                 trans = i == n - 1 ? 0u : ONE;
+  ProfileSink sink{s_cnt, s_fst, has_row ? i : PROFILE_NO_ROW};
+  if constexpr (HAS_AIR)  // phase 1: the AIR's K_air constraints
+    run_program((ConstWords)T->seg[s].code, (int)T->seg[s].ncode, slots, mainc, n, vt, vn, first,
+                last, trans, sink);
+  // phase 2: batches + 3 LogUp constraints; the challenges and the cumulative sum head qp
+  const ConstWords qw = (ConstWords)(const uint32_t*)&tab->seg[s].qp;
+  const RowCtx c{(ConstWords)T->seg[s].list, qw, mainc, T->seg[s].prepc, n, vt};
+  perm_constraints(c, T->seg[s].permc, vn, qw + QP_CUMSUM_WORD, first, last, trans, sink);
+  unsigned long long* res = T->seg[s].res;
+  profile_flush(s_cnt, s_fst, K, res + 2);
+  reduce_failures(sink.first, i, K, res);
+}
+
 namespace {
 constexpr int PERM_FREE_BATCHES = 5;  // 20 KiB: 8 blocks per CU, the wave limit (file header)
 
@@ -217,6 +272,7 @@ struct Prover {
   hipStream_t st;
   int nc = 0;
   std::vector<int> chip;     // m.chips index of the k-th committed matrix
+  std::vector<int> order;    // its position in the caller's arrays
   std::vector<size_t> hn;    // its height
   std::vector<DBuf<uint32_t>> evals, pe;
   std::vector<DBuf<EF>> rows;
@@ -225,6 +281,11 @@ struct Prover {
   Round mainr, permr, quotr;
   PermChallenges pch;
   DevTable perm_tab[2], quot_tab[2];  // permutation: the LDS classes; quotient: AIR, lookup-only
+  DevTable check_tab[2];              // the constraint check: AIR, lookup-only
+  int check_kmax[2] = {0, 0};         // the largest K of either check launch (its LDS tables)
+  std::vector<size_t> res_at;         // chip k's block in check_res: 2 + 2 K words
+  DBuf<unsigned long long> check_res;
+  std::vector<unsigned long long> check_host;
   std::vector<const QuotParams*> qp_dev;  // chip k's block inside its quotient table
   std::vector<const uint32_t*> sel;
 
@@ -241,44 +302,11 @@ struct Prover {
   }
 
   // Checks, upload and transpose (uni_upload_trace), the commit order, the main commit.
+  // lde = false (the constraint check) stops after the transposed evaluations.
   void commit_main(const int* chips, const uint32_t* const* traces, const size_t* heights, size_t n,
-                   bool tree = true) {
+                   bool tree = true, bool lde = true) {
     if (!m.can_prove) throw std::runtime_error("machine: a verifier-only machine cannot prove");
-    if (!chips || !traces || !heights || n == 0) throw std::runtime_error("machine: no traces");
-    if (n > m.chips.size()) throw std::runtime_error("machine: more traces than chips");
-    std::vector<bool> seen(m.chips.size(), false);
-    for (size_t i = 0; i < n; i++) {
-      const int c = chips[i];
-      if (c < 0 || (size_t)c >= m.chips.size() || seen[c])
-        throw std::runtime_error("machine: bad or repeated chip index");
-      seen[c] = true;
-      const MachineChip& ch = m.chips[c];
-      const size_t h = heights[i];
-      if (!traces[i]) throw std::runtime_error("machine: null trace for " + ch.name);
-      if (h < 1 || (h & (h - 1)) || h > ((size_t)1 << 23))
-        throw std::runtime_error("machine: height not a power of two in [1, 2^23] for " + ch.name);
-      if (ch.p.lk.prep_w && h != ch.prep_height)
-        throw std::runtime_error("machine: chip " + ch.name + " is not at its preprocessed height");
-    }
-    for (int pc : m.prep_chips)
-      if (!seen[pc])
-        throw std::runtime_error("machine: chip " + m.chips[pc].name +
-                                 " has preprocessed columns and must be included");
-    if (tree)  // the machine prover's own limit (the commit has none, merkle.hip)
-      for (size_t i = 0; i < n; i++) {
-        size_t same = 0;
-        for (size_t j = 0; j < n; j++) same += heights[j] == heights[i];
-        if (same > MACHINE_MAX_SAME_HEIGHT)
-          throw std::runtime_error("machine: " + std::to_string(same) + " chips of height " +
-                                   std::to_string(heights[i]) + ", a proof takes at most " +
-                                   std::to_string(MACHINE_MAX_SAME_HEIGHT) + " of one height");
-      }
-    std::vector<int> order(n);
-    for (size_t i = 0; i < n; i++) order[i] = (int)i;
-    std::sort(order.begin(), order.end(), [&](int a, int b) {  // (Reverse(height), name)
-      if (heights[a] != heights[b]) return heights[a] > heights[b];
-      return m.chips[chips[a]].name < m.chips[chips[b]].name;
-    });
+    order = machine_trace_order(m, chips, traces, heights, n, /*same_height_limit=*/tree);
     nc = (int)n;
     chip.resize(nc);
     hn.resize(nc);
@@ -293,6 +321,7 @@ struct Prover {
     for (int k = 0; k < nc; k++)
       evals[k] = uni_upload_trace((size_t)mc(k).p.lk.main_w, mc(k).name.c_str(),
                                   traces[order[k]], hn[k], st);
+    if (!lde) return;
     mainr.mats.resize(nc);
     for (int k = 0; k < nc; k++) commit_lde(mainr.mats[k], evals[k].p, hn[k], mc(k).p.lk.main_w, ONE, st);
     if (tree) mainr.commit(st, /*fetch_root=*/true);
@@ -349,6 +378,76 @@ struct Prover {
     if (tree) permr.commit(st, /*fetch_root=*/true);
     cums.resize(nc);
     HIP_CHECK(hipMemcpyAsync(cums.data(), cums_d.p, nc * sizeof(EF), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  }
+
+  // The constraint check's form of perm_commit: the running sums alone, no LDE.
+  void perm_sums() {
+    for (int k = 0; k < nc; k++)
+      perm_running_sum(rows[k].p, hn[k], pe[k].p, 4 * mc(k).p.lk.batches(), cums_d.p + k, st);
+    cums.resize(nc);
+    HIP_CHECK(hipMemcpyAsync(cums.data(), cums_d.p, nc * sizeof(EF), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  }
+
+  // The check's two segment tables (chips with an AIR, lookup-only chips) over the evaluations
+  // and the permutation rows where k_perm_rows_machine left them, and the result buffer: chip k's
+  // block is {~0, 0, count[K] = 0, first[K] = ~0} at 2 k + 2 (the sum of the earlier K).
+  void check_setup() {
+    res_at.resize(nc);
+    size_t words = 0;
+    for (int k = 0; k < nc; k++) {
+      res_at[k] = words;
+      words += 2 + 2 * (size_t)mc(k).p.num_constraints();
+    }
+    check_host.assign(words, 0);
+    check_res.reset(words);
+    MachTable T[2];
+    std::memset(T, 0, sizeof T);
+    for (int k = 0; k < nc; k++) {  // commit order: tallest first
+      const int K = mc(k).p.num_constraints();
+      unsigned long long* r = check_host.data() + res_at[k];
+      r[0] = ~0ull;
+      std::fill(r + 2 + K, r + 2 + 2 * K, ~0ull);
+      MachSeg sg{};
+      const ChipLists cl = lists(k);
+      sg.code = cl.code;
+      sg.ncode = (uint32_t)cl.ncode;
+      sg.list = cl.list;
+      sg.mainc = evals[k].p;
+      sg.prepc = prep_evals(k);
+      sg.permc = pe[k].p;
+      sg.res = check_res.p + res_at[k];
+      sg.log_rows = (uint32_t)log2i(hn[k]);
+      sg.num_constraints = (uint32_t)K;
+      sg.qp.perm_alpha = pch.alpha;
+      for (int j = 0; j < 8; j++) sg.qp.beta_pows[j] = pch.beta_pows[j];
+      sg.qp.cumsum = cums[k];
+      const int tb = cl.ncode > 0 ? 0 : 1;
+      push_segment(T[tb], sg, hn[k]);
+      check_kmax[tb] = std::max(check_kmax[tb], K);
+    }
+    upload_async(check_res.p, check_host.data(), words * sizeof(unsigned long long), st);
+    for (int tb = 0; tb < 2; tb++) check_tab[tb].upload(T[tb], st);
+  }
+  void check_segmented() {
+    if (check_tab[0].grid) {
+      hipLaunchKernelGGL(k_check_machine<1>, dim3(check_tab[0].grid), dim3(256),
+                         2 * (size_t)check_kmax[0] * sizeof(uint32_t), st, check_tab[0].d.p,
+                         check_kmax[0]);
+      KCHECK();
+    }
+    if (check_tab[1].grid) {
+      hipLaunchKernelGGL(k_check_machine<0>, dim3(check_tab[1].grid), dim3(256),
+                         2 * (size_t)check_kmax[1] * sizeof(uint32_t), st, check_tab[1].d.p,
+                         check_kmax[1]);
+      KCHECK();
+    }
+  }
+  void check_download() {
+    HIP_CHECK(hipMemcpyAsync(check_host.data(), check_res.p,
+                             check_host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                             st));
     HIP_CHECK(hipStreamSynchronize(st));
   }
 
@@ -600,6 +699,57 @@ std::vector<uint8_t> machine_prove(const MachineProgram& m, const int* chips,
   return std::move(w.b);
 }
 
+// machine_check's device path (machine_program.cpp refuses a verifier-only machine first): the
+// traces uploaded and transposed once, the permutation rows and running sums, the segmented
+// check.  Only the cumulative sums and the result words come back.
+MachineCheck machine_check_device(const MachineProgram& m, const int* chips,
+                                  const uint32_t* const* traces, const size_t* heights, size_t n,
+                                  Challenger& ch) {
+  if (api_lock_depth() == 0) throw std::logic_error("machine_check called outside the bfz API lock");
+  hipStream_t st = stream();
+  CallEnd end{st};
+  Prover P(m, st);
+  P.commit_main(chips, traces, heights, n, /*tree=*/false, /*lde=*/false);
+  const int nc = P.nc;
+  MachineCheck out;
+  out.alpha = ch.sample_ef();  // machine.rs:300-303
+  out.beta = ch.sample_ef();
+  P.perm_setup(out.alpha, out.beta);
+  P.perm_rows_segmented();
+  P.perm_sums();
+  P.check_setup();
+  P.check_segmented();
+  P.check_download();
+
+  std::vector<size_t> k0(n + 1, 0);  // the profile's prefix sums, in the caller's order
+  for (size_t i = 0; i < n; i++) k0[i + 1] = k0[i] + (size_t)m.chips[chips[i]].p.num_constraints();
+  out.chips.resize(n);
+  out.counts.resize(k0[n]);
+  out.first_rows.resize(k0[n]);
+  out.cumsum = ef_zero();
+  out.ok = true;
+  for (int k = 0; k < nc; k++) {
+    const size_t i = (size_t)P.order[k];
+    const int K = P.mc(k).p.num_constraints();
+    const unsigned long long* r = P.check_host.data() + P.res_at[k];
+    ChipCheck& cc = out.chips[i];
+    cc.chip = P.chip[k];
+    cc.height = P.hn[k];
+    cc.num_constraints = K;
+    cc.num_batches = P.mc(k).p.lk.batches();
+    cc.cumsum = P.cums[k];
+    decode_check_result(r, cc);
+    for (int j = 0; j < K; j++) {
+      out.counts[k0[i] + j] = r[2 + j];
+      out.first_rows[k0[i] + j] = r[2 + K + j] == ~0ull ? -1 : (int64_t)r[2 + K + j];
+    }
+    out.cumsum = ef_add(out.cumsum, P.cums[k]);
+    out.ok = out.ok && cc.failing_rows == 0;
+  }
+  out.ok = out.ok && ef_is_zero(out.cumsum);
+  return out;
+}
+
 void machine_time(const MachineProgram& m, const int* chips, const uint32_t* const* traces,
                   const size_t* heights, size_t n, int runs, float* perm_ms, float* quot_ms) {
   if (api_lock_depth() == 0) throw std::logic_error("machine_time called outside the bfz API lock");
@@ -711,6 +861,8 @@ void machine_time(const MachineProgram& m, const int* chips, const uint32_t* con
 // kernels a machine proof launches beside the built-in prover's (gpu.h PreloadKernels)
 static PreloadKernels preload_machine_program{(const void*)&k_quotient_machine<0>,
                                               (const void*)&k_quotient_machine<1>,
-                                              (const void*)&k_perm_rows_machine<1>};
+                                              (const void*)&k_perm_rows_machine<1>,
+                                              (const void*)&k_check_machine<0>,
+                                              (const void*)&k_check_machine<1>};
 
 }  // namespace bfz
