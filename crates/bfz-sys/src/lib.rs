@@ -653,6 +653,9 @@ extern "C" {
     pub fn bfz_set_pcs_variant(observe_openings: c_int) -> c_int;
     /// The largest constraint degree the `bfz_air_*` calls accept: 3..=9, 0 = the default (3).
     pub fn bfz_set_air_max_degree(degree: c_int) -> c_int;
+    /// The largest AIR degree a chip program may have (`bfz_chip_*`, `bfz_machine_*`): 3..=9,
+    /// 0 = the default (3); independent of `bfz_set_air_max_degree`.
+    pub fn bfz_set_chip_max_degree(degree: c_int) -> c_int;
     /// Test-only fault injection (bit 0: perturb the device challenger); 0 = off.
     pub fn bfz_set_fault_injection(mask: c_int) -> c_int;
 

@@ -883,10 +883,12 @@ int bfz_lookups_multiplicities(const uint8_t* table_prog, size_t table_len,
  * [1, 2^23], words >= p refused with the same message, air NULL / air_len 0 for a lookup-only
  * chip (Program, Memory and Byte have that shape), prep NULL when prep_width is 0.  The pair is
  * validated first: either program's own refusal, the AIR's width against main_width, an AIR degree
- * above 3, and a pair without an interaction (that is an AIR alone: the bfz_air_ calls).
+ * above the chip cap (3 unless bfz_set_chip_max_degree raised it), and a pair without an
+ * interaction (that is an AIR alone: the bfz_air_ calls).
  *
  *   bfz_chip_info        host only: the pair's shape.  For a built-in chip's two exported programs
- *                        num_constraints is the count bfz_check_chip reports.
+ *                        num_constraints is the count bfz_check_chip reports.  degree =
+ *                        max(AIR degree, 3), log_quotient_degree = log2_ceil(degree - 1).
  *   bfz_chip_check_rows  debug_constraints of ONE caller-defined chip, with bfz_check_chip's contract
  *                        and result struct (chip = -1).  perm: height x 4 * perm_width as
  *                        bfz_lookups_perm_trace returns it.  on_device = 0: a single-threaded host
@@ -899,7 +901,12 @@ int bfz_lookups_multiplicities(const uint8_t* table_prog, size_t table_len,
  *                        is read.  quot_alpha is the constraint-folding challenge.  *out (bfz_free):
  *                        2 * height x 4 words, row i = Q(3 w_2n^i) in natural order (quotient chunk
  *                        i mod 2, chunk row i >> 1).  Q is a polynomial of degree < 2 * height
- *                        exactly when every constraint holds on the trace. */
+ *                        exactly when every constraint holds on the trace.  A pair of AIR degree
+ *                        above 3 (D = 2^log_quotient_degree = 4 or 8 chunks, height at most
+ *                        2^(24 - log_quotient_degree)): *out is D * height x 4 words, row i =
+ *                        Q(3 w_(D height)^i) (chunk i mod D, chunk row i / D), built from coset
+ *                        slab 0 through k_quotient_chip_prog and the further slabs through
+ *                        k_quotient_machine_coset; Q then has degree < D * height. */
 typedef struct {
   int32_t main_width, prep_width, perm_width, n_interactions;   /* perm_width in EF columns */
   int32_t air_constraints, num_constraints, degree, log_quotient_degree;
@@ -959,11 +966,22 @@ int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const u
  *                        bfz_open.  *proof (bfz_free): BFZ1 whose chip words are those indices; a
  *                        machine without preprocessed columns has three input rounds per query.
  *                        A trace that violates a constraint still proves; the verifier rejects.
+ *                        Chips of AIR degree above 3 (bfz_set_chip_max_degree): every chip is
+ *                        checked against the cap in force again ("machine: chip NAME: chip
+ *                        program: AIR degree ..."), and a chip of log quotient degree l > 1 is
+ *                        refused above height 2^(24 - l) ("machine: height H of chip NAME is above
+ *                        2^(24 - l) at log quotient degree l"), both before any device work.  In
+ *                        BFZ1 such a chip has 2^l quotient chunks of 4 EF (the chunk-count word
+ *                        that is 2 for every other chip), chunk j on 3 w_(2^l n)^j H_n, and the
+ *                        quotient round holds the sum of the chips' chunk counts.
  *   bfz_machine_verify   host only; returns 0 whenever the check RAN, like bfz_uni_verify.  In
  *                        order: shapes, the transcript, the sum of the cumulative sums
  *                        ("cumulative sums do not sum to zero"; before the out-of-domain check, so
  *                        that a changed sum is named as such), per chip the out-of-domain check
- *                        ("OOD evaluation mismatch on chip NAME"), the PCS verification.
+ *                        ("OOD evaluation mismatch on chip NAME"), the PCS verification.  The
+ *                        shapes come from the machine's programs: a chip's chunk count is its
+ *                        2^l ("opened-value shape mismatch" otherwise), its log degree at most
+ *                        24 - l for l > 1, and the cap in force is checked as in bfz_machine_prove.
  *   bfz_machine_verify_batch  bfz_machine_verify of n proofs of one machine, with
  *                        bfz_verify_batch's contract: chs[i] is proof i's challenger after
  *                        bfz_machine_observe and is advanced as bfz_machine_verify advances it;
@@ -989,6 +1007,11 @@ int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const u
  *                        (k_perm_rows_prog, k_quotient_chip_prog) on the same device inputs,
  *                        alternating after one warm-up of each, whose words are compared.
  *                        perm_ms / quot_ms: 2 * runs floats, the segmented form's then the loop's.
+ *                        With chips of AIR degree above 3, quot_ms of both forms also covers the
+ *                        further coset slabs: per slab the chips' LDEs on it, the launches (one
+ *                        k_quotient_machine_coset per class against one per chip, every segment
+ *                        table uploaded before the timed runs) and the two chunks' LDEs.  Heights
+ *                        and the cap are refused as by bfz_machine_prove.
  *   bfz_machine_check    StarkMachine::debug_constraints (crates/stark/src/machine.rs:288-387) for
  *                        the machine, the call to run before any proof: alpha then beta are
  *                        sampled from ch (two sample_ext_element; ch is advanced, as in
@@ -1062,9 +1085,21 @@ int bfz_set_pcs_variant(int observe_openings);
  * included, with "uni_stark: constraint degree above <cap> is not supported".  Degrees 4 and 5
  * give log_quotient_degree 2 (4 quotient chunks), 6 to 9 give 3 (8 chunks); the height is then at
  * most 2^(24 - log_quotient_degree).  Nothing else is opted in: the built-in chips are what they
- * are, and chip programs and machines (bfz_chip_*, bfz_machine_*) keep their own refusal of an
- * AIR degree above 3 and stay at log quotient degree 1 whatever this switch says. */
+ * are, and chip programs and machines (bfz_chip_*, bfz_machine_*) keep a cap of their own
+ * (bfz_set_chip_max_degree) whatever this switch says. */
 int bfz_set_air_max_degree(int degree);
+
+/* The largest AIR degree a chip program (bfz_chip_*, bfz_machine_*) may have: 3..9, or 0 = the
+ * default, 3; any other value is an error that names the "chip max degree".  Process-wide and
+ * independent of bfz_set_air_max_degree: with the cap at c a chip's AIR compiles up to degree c
+ * whatever the AIR cap is, and above it the refusal is "chip program: AIR degree <d> is above <c>
+ * (log quotient degree <l>)".  A chip has degree max(AIR degree, 3) and log quotient degree
+ * log2_ceil(degree - 1): 2 for degrees 4 and 5 (4 quotient chunks), 3 for 6 to 9 (8 chunks); a
+ * lookup-only chip stays at (3, 1).  A chip of log quotient degree l above 1 takes heights up to
+ * 2^(24 - l).  The cap is read where a program is compiled and again by bfz_machine_prove,
+ * bfz_machine_time and bfz_machine_verify*: a machine created under a higher cap than the one in
+ * force is refused there with the same message. */
+int bfz_set_chip_max_degree(int degree);
 
 /* Test-only fault injection, no reference counterpart: bit 0 perturbs the device challenger's
  * uploaded sponge state, so the host's replay of the device-sampled challenges must fail the

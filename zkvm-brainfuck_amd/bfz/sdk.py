@@ -1639,7 +1639,9 @@ def chip_quotient(air: Optional[bytes], lookups: Optional[bytes], main, prep, al
     crates/stark/src/quotient.rs:18-165) on 3 H_2n.  chip = -1 runs the two programs; chip >= 0
     (air = lookups = None) runs that built-in chip's compiled kernel.  perm = None: the
     permutation trace and cumulative sum are computed on the device; otherwise both are the
-    caller's.  Returns (q, cumsum): q is (2 * height, 4) Montgomery words, row i = Q(3 w_2n^i)."""
+    caller's.  Returns (q, cumsum): q is (2 * height, 4) Montgomery words, row i = Q(3 w_2n^i).
+    A pair of AIR degree above 3 (set_chip_max_degree) has D = 2^log_quotient_degree = 4 or 8
+    chunks: q is then (D * height, 4), row i = Q(3 w_(D height)^i)."""
     import numpy as np
     init()
     if chip >= 0:
@@ -1659,7 +1661,7 @@ def chip_quotient(air: Optional[bytes], lookups: Optional[bytes], main, prep, al
         perm.ctypes.data_as(u32p) if perm is not None else None, main.shape[0],
         (ctypes.c_uint32 * 4)(*alpha), (ctypes.c_uint32 * 4)(*beta), cs,
         (ctypes.c_uint32 * 4)(*quot_alpha), ctypes.byref(out)))
-    q = np.ctypeslib.as_array(out, shape=(2 * main.shape[0], 4)).copy()
+    q = np.ctypeslib.as_array(out, shape=(main.shape[0] << info.log_quotient_degree, 4)).copy()
     lib().bfz_free(out)
     return q, list(cs)
 
@@ -1913,8 +1915,17 @@ def set_num_queries(q: int) -> None:
 def set_air_max_degree(degree: int) -> None:
     """The largest constraint degree air_info / air_check / air_prove / air_verify accept: 3..9,
     0 = the default (3).  Degrees 4 and 5 prove with 4 quotient chunks, 6 to 9 with 8.  Chip
-    programs and machines keep their own limit of 3."""
+    programs and machines keep a cap of their own (set_chip_max_degree)."""
     check(lib().bfz_set_air_max_degree(int(degree)))
+
+
+def set_chip_max_degree(degree: int) -> None:
+    """The largest AIR degree a chip program (chip_info, chip_quotient, Machine) may have: 3..9,
+    0 = the default (3); independent of set_air_max_degree.  A chip of AIR degree 4 or 5 has log
+    quotient degree 2 (4 quotient chunks), 6 to 9 has 3 (8 chunks), and takes heights up to
+    2^(24 - log quotient degree).  A machine made under a raised cap proves and verifies only while
+    the cap still admits its chips."""
+    check(lib().bfz_set_chip_max_degree(int(degree)))
 
 
 def set_pcs_variant(observe_openings: int) -> None:

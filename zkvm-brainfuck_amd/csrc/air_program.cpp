@@ -39,9 +39,9 @@ void set_air_max_degree(int degree) {
   g_max_degree.store(degree ? degree : AIR_DEFAULT_MAX_DEGREE, std::memory_order_relaxed);
 }
 
-void air_degree_throw() {
-  throw std::runtime_error("uni_stark: constraint degree above " + std::to_string(air_max_degree()) +
-                           " is not supported");
+void air_degree_throw(int cap, int degree) {
+  throw AirDegreeError("uni_stark: constraint degree above " + std::to_string(cap) +
+                           " is not supported", degree);
 }
 
 // Z_H(x) = x^n - 1 at x = 3 g^r w_2n^i: g^n = w_D, w_2n^n = -1.
@@ -61,7 +61,7 @@ SlabParams slab_params(size_t n, int lqd, int r, const kb::EF* alpha_pows) {
   return sp;
 }
 
-AirProgram air_compile(const uint8_t* prog, size_t len) {
+AirProgram air_compile(const uint8_t* prog, size_t len, int max_degree) {
   if (!prog || len < 16) bad("shorter than its header", 0);
   if (word_at(prog, 0) != AIR_MAGIC) bad("bad magic, expected \"BFA1\"", 0);
   const uint32_t width = word_at(prog, 1), nn = word_at(prog, 2), K = word_at(prog, 3);
@@ -124,7 +124,8 @@ AirProgram air_compile(const uint8_t* prog, size_t len) {
   }
   int lqd = 0;  // log2_ceil(degree - 1), at least 0 (uni_air_shape)
   while ((1 << lqd) < degree - 1) lqd++;
-  if (degree > air_max_degree()) air_degree_throw();
+  const int cap = max_degree < 0 ? air_max_degree() : max_degree;
+  if (degree > cap) air_degree_throw(cap, degree);
 
   // ---- compile.  uses[i]: reads of node i by reachable nodes and by constraints still ahead.
   std::vector<uint32_t> uses(nn, 0);

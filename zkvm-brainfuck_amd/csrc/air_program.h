@@ -16,6 +16,8 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "../../include/bfz.h"
@@ -45,17 +47,24 @@ struct AirProgram {
 };
 
 // The largest constraint degree the AIR-program path accepts (bfz_set_air_max_degree): 3 unless
-// raised, 9 at most (8 quotient chunks).  Process-wide; chip_compile keeps its own limit of 3.
+// raised, 9 at most (8 quotient chunks).  Process-wide; chip_compile keeps a cap of its own
+// (chip_program.h chip_max_degree).
 constexpr int AIR_DEFAULT_MAX_DEGREE = 3, AIR_TOP_MAX_DEGREE = 9;
 int air_max_degree();
 void set_air_max_degree(int degree);  // 0 = the default; throws outside {0, 3..9}
 // uni_dims_or_throw's message for a degree above the cap in force.
-[[noreturn]] void air_degree_throw();
+// It throws an AirDegreeError, which carries the refused degree (0 where the caller has none) so
+// that chip_compile can refuse in its own words.
+struct AirDegreeError : std::runtime_error {
+  int degree;
+  AirDegreeError(const std::string& what, int d) : std::runtime_error(what), degree(d) {}
+};
+[[noreturn]] void air_degree_throw(int cap = air_max_degree(), int degree = 0);
 
-// Throws std::runtime_error: a malformed program, a degree above air_max_degree()
-// (uni_dims_or_throw's message), more than BFZ_AIR_MAX_LIVE live values.  Reads nothing outside
-// [prog, prog + len).
-AirProgram air_compile(const uint8_t* prog, size_t len);
+// Throws std::runtime_error: a malformed program, a degree above max_degree (uni_dims_or_throw's
+// message; negative = air_max_degree()), more than BFZ_AIR_MAX_LIVE live values.  Reads nothing
+// outside [prog, prog + len).
+AirProgram air_compile(const uint8_t* prog, size_t len, int max_degree = -1);
 
 // The BFA1 bytes of a built-in chip's AIR; refuses the chips uni_air_shape_or_throw refuses.
 std::vector<uint8_t> air_export(int chip);

@@ -55,37 +55,7 @@ __global__ __launch_bounds__(256) void k_quotient_prog(const uint32_t* __restric
   for (int e = 0; e < 4; e++) qo.chunk[chunk][e * qo.stride + pos] = q.c[e];
 }
 
-// 1 / d for the block's 256 values d (none zero) with one field inversion: an inclusive prefix
-// and an inclusive suffix product inside each wave by shuffles (6 steps each), the four wave
-// totals through LDS, one minv of the block's product by thread 0, and
-//   1 / d_i = (product before i) (product after i) / (product of all).
-// Every thread of the block calls it (two barriers).
-__device__ __forceinline__ uint32_t block_inverse(uint32_t d, uint32_t* s_wave, uint32_t* s_tinv) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t pre = d, suf = d;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t up = __shfl_up(pre, off, 64), dn = __shfl_down(suf, off, 64);
-    if (lane >= (uint32_t)off) pre = mmul(pre, up);
-    if (lane + off < 64) suf = mmul(suf, dn);
-  }
-  if (lane == 63) s_wave[wave] = pre;  // the wave's product
-  __syncthreads();
-  if (threadIdx.x == 0)
-    *s_tinv = minv(mmul(mmul(s_wave[0], s_wave[1]), mmul(s_wave[2], s_wave[3])));
-  // the product before / after the thread's own value: inside the wave, then the other waves
-  uint32_t before = __shfl_up(pre, 1, 64), after = __shfl_down(suf, 1, 64);
-  if (lane == 0) before = ONE;
-  if (lane == 63) after = ONE;
-#pragma unroll
-  for (uint32_t k = 0; k < 4; k++) {
-    const uint32_t wk = s_wave[k];
-    if (k < wave) before = mmul(before, wk);
-    if (k > wave) after = mmul(after, wk);
-  }
-  __syncthreads();
-  return mmul(mmul(before, after), *s_tinv);
-}
+// block_inverse is in air_program_dev.h (machine_program.hip runs it too).
 
 // k_quotient_prog<1> on a coset slab S_r = 3 g^r H_2n, r >= 1, of the quotient domain 3 H_(D n)
 // (air_program.h SlabParams): one thread per slab point, the slot file and the scalar list as

@@ -1787,6 +1787,8 @@ struct ChipQuotSetup {
   int mw, pw, permw, K;
   size_t n;
   bfz::DBuf<uint32_t> code, list, lm, lp, le, qout;
+  bfz::DBuf<uint32_t> mc, pc, pe;  // the evaluations: the slabs of a pair of degree above 3 extend them
+  int lqd = 1;                     // 2^lqd chunks
   bfz::DBuf<kb::EF> apows;
   bfz::DBuf<bfz::QuotParams> qpd;
   bfz::QuotParams qp;
@@ -1812,16 +1814,20 @@ struct ChipQuotSetup {
       pw = p.lk.prep_w;
       permw = p.perm_width();
       K = p.num_constraints();
+      lqd = p.log_quotient_degree();
     }
     if (n == 0 || (n & (n - 1)) || n > ((size_t)1 << 23))
       throw std::runtime_error("chip_quotient: height not a power of two in [1, 2^23]");
+    if (chip < 0 && n > bfz::chip_max_height(p))  // the quotient domain 3 H_(D n) must exist
+      throw std::runtime_error("chip_quotient: height " + std::to_string(n) + " is above 2^" +
+                               std::to_string(24 - lqd) + " at log quotient degree " +
+                               std::to_string(lqd));
     if (pw && !prep) throw std::runtime_error("chip_quotient: the chip has preprocessed columns");
     const bfz::PermChallenges ch = lookup_challenges(alpha, beta);
     const kb::EF qa = ef_arg(quot_alpha, "challenge");
     if (perm) cumsum = ef_arg(cumsum_in, "cumulative sum");
 
-    const bfz::DBuf<uint32_t> mc = bfz::uni_upload_trace((size_t)mw, "chip", main, n, st);
-    bfz::DBuf<uint32_t> pc, pe;
+    mc = bfz::uni_upload_trace((size_t)mw, "chip", main, n, st);
     if (pw) pc = bfz::uni_upload_trace((size_t)pw, "chip", prep, n, st);
     if (chip < 0) {
       list.reset(p.lk.list.size());
@@ -1867,14 +1873,15 @@ struct ChipQuotSetup {
     qp.cumsum = cumsum;
     qpd.reset(1);
     bfz::upload_async(qpd.p, &qp, sizeof(qp), st);
-    qout.reset(8 * n);
+    qout.reset((4 * n) << lqd);
     HIP_CHECK(hipStreamSynchronize(st));  // the uploads' host sources end with this constructor
   }
 
   // One launch of the quotient kernel: the compiled template of `chip`, or the programs'.
   void launch(bool compiled, hipStream_t st) {
     const int logN = bfz::log2i(n) + 1;
-    const bfz::QuotOut qo{{qout.p, qout.p + 4 * n}, n};
+    const size_t half = (size_t)1 << (lqd - 1);  // slab 0 holds chunks 0 and D/2
+    const bfz::QuotOut qo{{qout.p, qout.p + 4 * n * half}, n};
     if (compiled) {
       bfz::QuotRows in{lm.p, lm.p, le.p, le.p, pw ? lp.p : nullptr, 2 * n, 0, 2 * n, {}, {}};
       for (int c = 0; c < 64; c++) in.nmain[c] = in.nperm[c] = (uint8_t)c;
@@ -1883,6 +1890,18 @@ struct ChipQuotSetup {
       const bfz::ChipLists cl{p.has_air ? code.p : nullptr, p.has_air ? (int)p.air.code.size() : 0,
                               list.p, p.air_constraints(), p.num_constraints()};
       bfz::quotient_chip_prog(cl, lm.p, pw ? lp.p : nullptr, le.p, logN, qp, qpd.p, qo, st);
+      // slabs 1 .. D/2 - 1 (chunks r and r + D/2) over the LDEs on 3 g^r H_2n, which replace
+      // slab 0's in the same buffers: at D > 2 launch() runs once per setup (bfz_chip_quotient;
+      // bfz_chip_quotient_time refuses such a pair)
+      for (size_t r = 1; r < half; r++) {
+        bfz::QuotParams sq = qp;
+        bfz::slab_quot_params(sq, n, lqd, (int)r);
+        bfz::coset_lde(mc.p, n, mw, sq.shift, lm.p, st);
+        if (pw) bfz::coset_lde(pc.p, n, pw, sq.shift, lp.p, st);
+        bfz::coset_lde(pe.p, n, 4 * permw, sq.shift, le.p, st);
+        bfz::quotient_chip_slab(cl, lm.p, pw ? lp.p : nullptr, le.p, logN, sq,
+                                bfz::QuotOut{{qout.p + 4 * n * r, qout.p + 4 * n * (r + half)}, n}, st);
+      }
     }
   }
 };
@@ -1987,16 +2006,16 @@ int bfz_chip_quotient(int chip, const uint8_t* air, size_t air_len, const uint8_
                     cumsum_io, quot_alpha, st);
     bfz::staging_reset();
     s.launch(chip >= 0, st);
-    const size_t n = height;
-    std::vector<uint32_t> q(8 * n);  // chunk c, component e at q[(4 c + e) n + position]
+    const size_t n = height, D = (size_t)1 << s.lqd;
+    std::vector<uint32_t> q(4 * D * n);  // chunk c, component e at q[(4 c + e) n + position]
     HIP_CHECK(hipMemcpyAsync(q.data(), s.qout.p, q.size() * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     bfz::staging_reset();
-    uint32_t* o = (uint32_t*)std::malloc(8 * n * 4 + 4);
+    uint32_t* o = (uint32_t*)std::malloc(q.size() * 4 + 4);
     if (!o) throw std::runtime_error("out of host memory");
-    const int logN = bfz::log2i(n) + 1;
-    for (size_t i = 0; i < 2 * n; i++) {  // storage position t = bitrev(i): chunk t >> log n
-      const size_t t = bfz::bitrev32((uint32_t)i, logN), c = t / n, pos = t & (n - 1);
+    const int logn = bfz::log2i(n);
+    for (size_t i = 0; i < D * n; i++) {  // point i: chunk i mod D, chunk row i / D, bit-reversed
+      const size_t c = i % D, pos = logn ? bfz::bitrev32((uint32_t)(i / D), logn) : 0;
       for (int e = 0; e < 4; e++) o[4 * i + e] = q[(4 * c + e) * n + pos];
     }
     std::memcpy(cumsum_io, s.cumsum.c, 16);
@@ -2020,6 +2039,10 @@ int bfz_chip_quotient_time(int chip, const uint8_t* air, size_t air_len, const u
     if (s.mw != bfz::CHIP_INFO[chip].main_w || s.pw != bfz::CHIP_INFO[chip].prep_w ||
         s.permw != bfz::perm_width(chip) || s.K != bfz::num_constraints(chip))
       throw std::runtime_error("chip_quotient_time: the programs do not have the chip's shape");
+    // (launch() leaves the last slab's LDEs where slab 0's were: one call per setup at D > 2)
+    if (s.lqd > 1)
+      throw std::runtime_error("chip_quotient_time: the programs' AIR degree is above 3; the "
+                               "built-in chip it is timed against has two quotient chunks");
     s.chip = chip;
     hipEvent_t e0, e1;
     HIP_CHECK(hipEventCreate(&e0));
@@ -2713,6 +2736,13 @@ int bfz_set_num_queries(int q) {
 int bfz_set_air_max_degree(int degree) {
   return guarded([&] {
     bfz::set_air_max_degree(degree);
+    return 0;
+  });
+}
+
+int bfz_set_chip_max_degree(int degree) {
+  return guarded([&] {
+    bfz::set_chip_max_degree(degree);
     return 0;
   });
 }

@@ -3,6 +3,7 @@
 #include "chip_program.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -10,6 +11,41 @@
 namespace bfz {
 
 using namespace kb;
+
+namespace {
+std::atomic<int> g_chip_max_degree{AIR_DEFAULT_MAX_DEGREE};
+}
+
+int chip_max_degree() { return g_chip_max_degree.load(std::memory_order_relaxed); }
+
+void set_chip_max_degree(int degree) {
+  if (degree != 0 && (degree < AIR_DEFAULT_MAX_DEGREE || degree > AIR_TOP_MAX_DEGREE))
+    throw std::runtime_error("chip max degree must be in [3, 9] (0 = the default, 3)");
+  g_chip_max_degree.store(degree ? degree : AIR_DEFAULT_MAX_DEGREE, std::memory_order_relaxed);
+}
+
+namespace {
+[[noreturn]] void chip_degree_throw(int degree, int cap) {
+  throw std::runtime_error("chip program: AIR degree " + std::to_string(degree) + " is above " +
+                           std::to_string(cap) + " (log quotient degree " +
+                           std::to_string(ChipProgram::chip_lqd_of_degree(cap)) + ")");
+}
+}  // namespace
+
+void chip_cap_or_throw(const ChipProgram& p) {
+  const int cap = chip_max_degree();
+  if (p.has_air && p.air.degree > cap) chip_degree_throw(p.air.degree, cap);
+}
+
+void slab_quot_params(QuotParams& qp, size_t n, int lqd, int r) {
+  const SlabParams sp = slab_params(n, lqd, r, qp.alpha_pows);
+  qp.shift = sp.shift;
+  qp.zh_even = sp.zh_even;
+  qp.zh_odd = sp.zh_odd;
+  qp.zh_even_inv = sp.zh_even_inv;
+  qp.zh_odd_inv = sp.zh_odd_inv;
+  qp.wn_inv = sp.wn_inv;
+}
 
 ChipProgram chip_compile(const uint8_t* air, size_t air_len, const uint8_t* lookups,
                          size_t lookups_len) {
@@ -26,10 +62,20 @@ ChipProgram chip_compile(const uint8_t* air, size_t air_len, const uint8_t* look
   p.lk = lookups_compile(lookups, lookups_len);
   p.has_air = air != nullptr && air_len != 0;
   if (p.has_air) {
-    p.air = air_compile(air, air_len);  // (refuses a degree above air_max_degree() itself)
-    if (p.air.degree > 3)  // whatever that cap: a chip's quotient has two chunks
-      throw std::runtime_error("chip program: AIR degree " + std::to_string(p.air.degree) +
-                               " is above 3 (log quotient degree 1)");
+    // At the default cap the AIR path's own cap refuses first, in its own words, as it always
+    // has.  A raised chip cap stands alone: air_compile refuses above it before it compiles
+    // anything, and that refusal is reworded into the chip's.
+    const int cap = chip_max_degree();
+    if (cap == AIR_DEFAULT_MAX_DEGREE) {
+      p.air = air_compile(air, air_len);
+    } else {
+      try {
+        p.air = air_compile(air, air_len, cap);
+      } catch (const AirDegreeError& e) {
+        chip_degree_throw(e.degree, cap);
+      }
+    }
+    chip_cap_or_throw(p);
     if (p.air.width != p.lk.main_w)
       throw std::runtime_error("chip program: the AIR's width " + std::to_string(p.air.width) +
                                " is not the interactions' main width " +

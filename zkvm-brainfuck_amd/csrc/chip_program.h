@@ -26,14 +26,33 @@ struct ChipProgram {
   int air_constraints() const { return has_air ? air.num_constraints : 0; }
   int num_constraints() const { return air_constraints() + lk.batches() + 3; }  // K
   int perm_width() const { return lk.perm_width(); }                            // EF columns
-  // chip.rs:82-87: a chip with an interaction has degree max(AIR degree, 3) and chip_compile
-  // refuses an AIR degree above 3, so the log quotient degree is 1 whatever the AIR
-  int degree() const { return 3; }
-  int log_quotient_degree() const { return 1; }
+  // chip.rs:82-87: a chip with an interaction has degree max(AIR degree, 3) and log quotient
+  // degree log2_ceil(degree - 1): 1 up to degree 3, 2 for 4 and 5, 3 for 6 to 9
+  int degree() const { return has_air && air.degree > 3 ? air.degree : 3; }
+  int log_quotient_degree() const { return chip_lqd_of_degree(degree()); }
+  int chunks() const { return 1 << log_quotient_degree(); }  // D
+  static int chip_lqd_of_degree(int d) {
+    int l = 1;
+    while ((1 << l) < d - 1) l++;
+    return l;
+  }
 };
 
+// The largest AIR degree a chip program may have (bfz_set_chip_max_degree): 3 unless raised, 9 at
+// most.  Process-wide and independent of air_max_degree().  A program compiled under a higher cap
+// is refused again where it is used (chip_cap_or_throw: machine_prove, machine_verify).
+int chip_max_degree();
+void set_chip_max_degree(int degree);  // 0 = the default; throws outside {0, 3..9}
+void chip_cap_or_throw(const ChipProgram& p);
+// A chip of log quotient degree l takes heights up to 2^(24 - l) (3 H_(D n) must exist); at l = 1
+// the bound is the 2^23 of every trace.
+inline size_t chip_max_height(const ChipProgram& p) {
+  return (size_t)1 << (p.log_quotient_degree() > 1 ? 24 - p.log_quotient_degree() : 23);
+}
+
 // air = nullptr / air_len = 0: a lookup-only chip.  Throws std::runtime_error naming what is
-// wrong: either program's own refusal, a width mismatch, no interaction, an AIR degree above 3.
+// wrong: either program's own refusal, a width mismatch, no interaction, an AIR degree above
+// chip_max_degree().
 ChipProgram chip_compile(const uint8_t* air, size_t air_len, const uint8_t* lookups,
                          size_t lookups_len);
 
@@ -69,6 +88,16 @@ void launch_quotient_chip_prog(const ChipLists& cl, const uint32_t* mainc, const
                                const uint32_t* permc, int logN, const QuotParams* qp_dev,
                                const uint32_t* twf, const uint32_t* sel_inv, const QuotOut& qo,
                                hipStream_t st);
+// A chip of D = 2^lqd = 4 or 8 chunks: its quotient on coset slab S_r = 3 g^r H_2n, r >= 1, of
+// 3 H_(D n) (air_program.h SlabParams).  slab_quot_params turns qp's domain fields (shift, Z_H
+// values and inverses) into the slab's and leaves the challenges, the cumulative sum and
+// alpha_pows.  quotient_chip_slab (machine_program.hip) is k_quotient_machine_coset over a
+// one-segment table: mainc / prepc / permc = the LDEs on the slab, out.chunk[0] / [1] = where
+// chunks r / r + D/2 go.
+void slab_quot_params(QuotParams& qp, size_t n, int lqd, int r);
+void quotient_chip_slab(const ChipLists& cl, const uint32_t* mainc, const uint32_t* prepc,
+                        const uint32_t* permc, int logN, const QuotParams& slab_qp,
+                        const QuotOut& out, hipStream_t st);
 // The row check of column-major bit-reversed traces of h rows, as check_chip_device: res =
 // {min(row * K + index) or ~0, failing rows}; per_row_dev (optional) by storage position.
 void check_chip_prog_device(const ChipLists& cl, const uint32_t* mainc, const uint32_t* prepc,

@@ -146,6 +146,74 @@ __global__ __launch_bounds__(256) void k_quotient_machine(const MachTable* __res
   for (int e = 0; e < 4; e++) dst[e * stride + pos] = q.c[e];
 }
 
+// k_quotient_machine on a coset slab S_r = 3 g^r H_2n, r >= 1, of the quotient domain 3 H_(D n) a
+// chip of AIR degree 4 to 9 needs (D = 2^lqd = 4 or 8 chunks, g = w_(D n); air_program.h
+// SlabParams has the geometry).  One launch covers every chip of the machine that has a slab r:
+// a segment's mainc / prepc / permc are the chip's LDEs ON THE SLAB (Prover::slab_ldes), and its
+// QuotParams block is the slab's -- shift = 3 g^r, the slab's two Z_H values and their inverses --
+// beside the chip's alpha powers, LogUp challenges and cumulative sum, so the kernel reads the
+// descriptor exactly as k_quotient_machine does.  What differs from it:
+//   - no selector table exists for a slab: the block's 256 denominators (x - 1)(x - w_n^-1) are
+//     inverted with one field inversion (block_inverse; a slab is disjoint from H_n, none is
+//     zero).  That needs barriers, so a thread past its segment brings the denominator 1, takes
+//     part in both barriers and leaves after them; a block never spans two segments, so the
+//     segment walk and everything read from the descriptor stay uniform across the barriers.
+//   - the slab's even natural points are chunk r and its odd ones chunk r + D/2: out[0] / out[1]
+//     are the two halves of the chip's 2 x 4 x n value buffer (stride n), which the host extends
+//     to the two chunks' LDEs.
+// LDS: the 32 KiB slot file (HAS_AIR = 1) + block_inverse's 20 bytes; HAS_AIR = 0 declares the 20
+// bytes alone.  (Only a chip with an AIR can have degree above 3, so today every slab segment is
+// in the HAS_AIR = 1 launch; the other class is kept so that the two quotient launches pair up.)
+template <int HAS_AIR>
+__global__ __launch_bounds__(256) void k_quotient_machine_coset(const MachTable* __restrict__ tab,
+                                                                const uint32_t* __restrict__ twf) {
+  uint32_t(*slots)[256] = nullptr;
+  if constexpr (HAS_AIR) {
+    __shared__ uint32_t file[BFZ_AIR_MAX_LIVE][256];
+    slots = file;
+  }
+  __shared__ uint32_t s_wave[4], s_tinv;
+  const ConstTable T = (ConstTable)tab;
+  const uint32_t s = find_segment(T);
+  const int logN = (int)T->seg[s].log_rows;
+  const uint32_t* mainc = T->seg[s].mainc;
+  const uint32_t* prepc = T->seg[s].prepc;
+  const uint32_t* permc = T->seg[s].permc;
+  const QuotParams* qpp = &tab->seg[s].qp;
+  const QuotParams qp = *qpp;  // device memory; uniform: scalar loads of the fields read below
+  const size_t N = (size_t)1 << logN, n = N >> 1;
+  const size_t t = (size_t)(blockIdx.x - T->off[s]) * blockDim.x + threadIdx.x;
+  const bool has_point = t < N;
+  const uint32_t i = dbitrev(has_point ? (uint32_t)t : 0u, logN);  // in bounds whatever t
+  const uint32_t x = quot_point(i, (uint32_t)n, qp.shift, twf);
+  const uint32_t a = msub(x, ONE), b = msub(x, qp.wn_inv);
+  const uint32_t inv_ab = block_inverse(has_point ? mmul(a, b) : ONE, s_wave, &s_tinv);
+  if (!has_point) return;  // (no barrier below)
+
+  const uint32_t inext = (i + 2) & (uint32_t)(N - 1);
+  const uint32_t vt = (uint32_t)t * 4u, vn = dbitrev(inext, logN) * 4u;  // t < 2^23
+  const uint32_t zh = (i & 1) ? qp.zh_odd : qp.zh_even;
+  const uint32_t zh_inv = (i & 1) ? qp.zh_odd_inv : qp.zh_even_inv;
+  const uint32_t zi = mmul(zh, inv_ab);
+  const uint32_t is_first = mmul(zi, b), is_last = mmul(zi, a), is_trans = b;
+
+  PowAcc acc{{0, 0, 0, 0}, 0, (ConstWords)qp.alpha_pows, 0};
+  if constexpr (HAS_AIR)  // phase 1: the AIR's K_air constraints
+    run_program((ConstWords)T->seg[s].code, (int)T->seg[s].ncode, slots, mainc, N, vt, vn, is_first,
+                is_last, is_trans, acc);
+  // phase 2: batches + 3 LogUp constraints
+  const ConstWords qw = (ConstWords)(const uint32_t*)qpp;
+  const RowCtx c{(ConstWords)T->seg[s].list, qw, mainc, prepc, N, vt};
+  perm_constraints(c, permc, vn, qw + QP_CUMSUM_WORD, is_first, is_last, is_trans, acc);
+
+  const EF q = ef_mul_base(acc.value(), zh_inv);
+  const size_t half = t >> (logN - 1), pos = t & (n - 1);
+  uint32_t* dst = T->seg[s].out[half];
+  const size_t stride = T->seg[s].out_stride;
+#pragma unroll
+  for (int e = 0; e < 4; e++) dst[e * stride + pos] = q.c[e];
+}
+
 // k_perm_rows_prog<1> for every segment of tab: one thread per storage position of a trace of
 // n = 2^log_rows rows; the batch columns of the segment's perm and rowsum[t].  Dynamic LDS: the
 // launch's largest batch count x 4 x LKP_T words (a thread's slots depend on its own batch index
@@ -265,6 +333,39 @@ struct DevTable {
   }
 };
 
+// A table of one segment: a chip's coset slab alone (bfz_chip_quotient, and machine_time's
+// per-chip form, which builds its tables before the timed window as the segmented form does).
+void one_slab_table(DevTable& dt, const ChipLists& cl, const uint32_t* mainc, const uint32_t* prepc,
+                    const uint32_t* permc, int logN, const QuotParams& slab_qp, const QuotOut& out,
+                    hipStream_t st) {
+  MachTable T;
+  std::memset(&T, 0, sizeof T);
+  MachSeg sg{};
+  sg.code = cl.code;
+  sg.ncode = (uint32_t)cl.ncode;
+  sg.list = cl.list;
+  sg.mainc = mainc;
+  sg.prepc = prepc;
+  sg.permc = permc;
+  sg.out[0] = out.chunk[0];
+  sg.out[1] = out.chunk[1];
+  sg.out_stride = out.stride;
+  sg.log_rows = (uint32_t)logN;
+  sg.qp = slab_qp;
+  push_segment(T, sg, (size_t)1 << logN);
+  dt.upload(T, st);
+}
+// Only a chip with an AIR exceeds degree 3, so every slab table there is today is has_air; the
+// HAS_AIR = 0 branch mirrors k_quotient_machine's pair and cannot be reached.
+void launch_slab_table(const DevTable& dt, bool has_air, hipStream_t st) {
+  const uint32_t* twf = (const uint32_t*)twiddles().fwd();
+  if (has_air)
+    hipLaunchKernelGGL(k_quotient_machine_coset<1>, dim3(dt.grid), dim3(256), 0, st, dt.d.p, twf);
+  else
+    hipLaunchKernelGGL(k_quotient_machine_coset<0>, dim3(dt.grid), dim3(256), 0, st, dt.d.p, twf);
+  KCHECK();
+}
+
 // One proof's device state, stage by stage (machine_prove runs them once; machine_time runs the
 // two interpreted steps in both forms on the same inputs).
 struct Prover {
@@ -288,6 +389,15 @@ struct Prover {
   std::vector<unsigned long long> check_host;
   std::vector<const QuotParams*> qp_dev;  // chip k's block inside its quotient table
   std::vector<const uint32_t*> sel;
+  std::vector<QuotParams> qph;            // the same block on the host (slab 0's domain fields)
+  std::vector<int> qat;                   // chip k's first matrix in the quotient round (D_k each)
+  // A chip of D = 4 or 8 chunks: its LDEs on one coset slab -- main, preprocessed, permutation in
+  // one buffer of 2n x (w_main + w_prep + 4 perm_width) that every slab reuses -- and the slab's
+  // 2 x 4 x n chunk values; slab_tab[r - 1]: the segment tables of slab r (AIR, lookup-only).
+  std::vector<DBuf<uint32_t>> slab, vals;
+  DevTable slab_tab[3][2];
+  std::vector<DevTable> chip_slab_tab;    // machine_time: chip k's slab r alone, at 3 k + r - 1
+  int max_half = 1;                       // the largest D / 2: slabs 1 .. max_half - 1 exist
 
   Prover(const MachineProgram& m_, hipStream_t s) : m(m_), st(s) {}
   const MachineChip& mc(int k) const { return m.chips[chip[k]]; }
@@ -316,6 +426,18 @@ struct Prover {
       chip[k] = chips[order[k]];
       hn[k] = heights[order[k]];
       tallest = std::max(tallest, hn[k]);
+    }
+    for (int k = 0; k < nc; k++) {  // before any device work
+      try {
+        chip_cap_or_throw(mc(k).p);
+      } catch (const std::exception& e) {
+        throw std::runtime_error("machine: chip " + mc(k).name + ": " + e.what());
+      }
+      if (lde && hn[k] > chip_max_height(mc(k).p))  // the quotient domain 3 H_(D n) must exist
+        throw std::runtime_error("machine: height " + std::to_string(hn[k]) + " of chip " + mc(k).name +
+                                 " is above 2^" + std::to_string(24 - mc(k).p.log_quotient_degree()) +
+                                 " at log quotient degree " +
+                                 std::to_string(mc(k).p.log_quotient_degree()));
     }
     twiddles().ensure(log2i(tallest) + 1);
     for (int k = 0; k < nc; k++)
@@ -451,12 +573,24 @@ struct Prover {
     HIP_CHECK(hipStreamSynchronize(st));
   }
 
-  // The chunk matrices (each chunk's own half written by the kernel, as the built-in prover
-  // places it), every chip's QuotParams block and the two segment tables.
+  // The chunk matrices (D_k per chip; chunks 0 and D_k / 2 get their own half from the kernel, as
+  // the built-in prover places it), every chip's QuotParams block, the two segment tables of
+  // slab 0 and those of the further slabs.
   void quot_setup(const EF& alpha) {
-    quotr.mats.resize(2 * nc);
-    size_t ktot = 0;
-    for (int k = 0; k < nc; k++) ktot += (size_t)mc(k).p.num_constraints();
+    qat.resize(nc);
+    qph.resize(nc);
+    size_t ktot = 0, nmat = 0;
+    for (int k = 0; k < nc; k++) {
+      ktot += (size_t)mc(k).p.num_constraints();
+      qat[k] = (int)nmat;
+      nmat += (size_t)mc(k).p.chunks();
+      max_half = std::max(max_half, mc(k).p.chunks() / 2);
+    }
+    quotr.mats.resize(nmat);
+    slab.resize(nc);
+    vals.resize(nc);
+    MachTable ST[3][2];
+    std::memset(ST, 0, sizeof ST);
     std::vector<EF> ap(ktot);
     apows_d.reset(ktot);
     MachTable T[2];
@@ -468,12 +602,13 @@ struct Prover {
     for (int k = 0; k < nc; k++) {
       const size_t n = hn[k];
       const int logn = log2i(n), K = mc(k).p.num_constraints();
-      const uint32_t w2n = two_adic_gen(logn + 1);
-      for (int cc = 0; cc < 2; cc++) {
-        CMat& qm = quotr.mats[2 * k + cc];
+      const int lqd = mc(k).p.log_quotient_degree(), D = 1 << lqd, half = D / 2;
+      const uint32_t g = two_adic_gen(logn + lqd);
+      for (int cc = 0; cc < D; cc++) {
+        CMat& qm = quotr.mats[qat[k] + cc];
         qm.n = n;
         qm.log_n = logn;
-        qm.shift = mmul(three, cc ? w2n : ONE);  // split_domains: shift * g^cc
+        qm.shift = mmul(three, mpow(g, (uint64_t)cc));  // split_domains: shift * g^cc
         qm.lde.height = 2 * n;
         qm.lde.width = 4;
         qm.lde.buf.reset(8 * n);
@@ -497,24 +632,46 @@ struct Prover {
       sg.prepc = prep_lde(k);
       sg.permc = permr.mats[k].lde.buf.p;
       sg.sel_inv = sel[k];
-      sg.out[0] = quotr.mats[2 * k].lde.buf.p;
-      sg.out[1] = quotr.mats[2 * k + 1].lde.buf.p + n;
+      sg.out[0] = quotr.mats[qat[k]].lde.buf.p;
+      sg.out[1] = quotr.mats[qat[k] + half].lde.buf.p + n;
       sg.out_stride = 2 * n;
       sg.log_rows = (uint32_t)(logn + 1);
       sg.qp = quot_params_of_height(n, apows_d.p + k0);
       sg.qp.perm_alpha = pch.alpha;
       for (int j = 0; j < 8; j++) sg.qp.beta_pows[j] = pch.beta_pows[j];
       sg.qp.cumsum = cums[k];
+      qph[k] = sg.qp;
       const int tb = cl.ncode > 0 ? 0 : 1;
       where[k] = {tb, (int)T[tb].nseg};
       push_segment(T[tb], sg, 2 * n);
+      if (half > 1) {  // slabs 1 .. half - 1: the same segment over the slab's LDEs and values
+        const int mw = mc(k).p.lk.main_w, pw = mc(k).p.lk.prep_w;
+        slab[k].reset(2 * n * (size_t)(mw + pw + 4 * mc(k).p.perm_width()));
+        vals[k].reset(8 * n);
+        sg.mainc = slab[k].p;
+        sg.prepc = pw ? slab[k].p + 2 * n * (size_t)mw : nullptr;
+        sg.permc = slab[k].p + 2 * n * (size_t)(mw + pw);
+        sg.sel_inv = nullptr;
+        sg.out[0] = vals[k].p;
+        sg.out[1] = vals[k].p + 4 * n;
+        sg.out_stride = n;
+        for (int r = 1; r < half; r++) {
+          slab_quot_params(sg.qp, n, lqd, r);
+          push_segment(ST[r - 1][tb], sg, 2 * n);
+        }
+      }
       k0 += (size_t)K;
     }
     upload_async(apows_d.p, ap.data(), ktot * sizeof(EF), st);
     for (int tb = 0; tb < 2; tb++) quot_tab[tb].upload(T[tb], st);
+    for (int r = 1; r < max_half; r++)
+      for (int tb = 0; tb < 2; tb++) slab_tab[r - 1][tb].upload(ST[r - 1][tb], st);
     qp_dev.resize(nc);
     for (int k = 0; k < nc; k++) qp_dev[k] = &quot_tab[where[k].first].d.p->seg[where[k].second].qp;
   }
+  // Slab 0 of every chip (the committed LDEs, the cached selector tables), then slab by slab the
+  // chips that have one: their LDEs, one launch per class, their two chunks' LDEs.  A machine of
+  // D = 2 chips launches slab 0 alone.
   void quotient_segmented() {
     const uint32_t* twf = (const uint32_t*)twiddles().fwd();
     if (quot_tab[0].grid) {
@@ -527,14 +684,68 @@ struct Prover {
                          quot_tab[1].d.p, twf);
       KCHECK();
     }
+    for (int r = 1; r < max_half; r++) {
+      slab_ldes(r);
+      for (int tb = 0; tb < 2; tb++)  // (tb = 1, lookup-only: empty today, launch_slab_table)
+        if (slab_tab[r - 1][tb].grid) launch_slab_table(slab_tab[r - 1][tb], tb == 0, st);
+      slab_chunks(r);
+    }
   }
+  // Every chip with a slab r: its three traces extended onto S_r = 3 g^r H_2n from the evaluations.
+  // The buffer is the one slab r - 1 used; the stream orders the reuse.
+  void slab_ldes(int r) {
+    for (int k = 0; k < nc; k++) {
+      if (mc(k).p.chunks() / 2 <= r) continue;
+      const size_t n = hn[k];
+      const int mw = mc(k).p.lk.main_w, pw = mc(k).p.lk.prep_w;
+      const uint32_t g = two_adic_gen(log2i(n) + mc(k).p.log_quotient_degree());
+      const uint32_t shift = mmul(to_mont(3), mpow(g, (uint64_t)r));
+      coset_lde(evals[k].p, n, mw, shift, slab[k].p, st);
+      if (pw) coset_lde(prep_evals(k), n, pw, shift, slab[k].p + 2 * n * (size_t)mw, st);
+      coset_lde(pe[k].p, n, 4 * mc(k).p.perm_width(), shift, slab[k].p + 2 * n * (size_t)(mw + pw), st);
+    }
+  }
+  // The slab's values are chunks r and r + D/2 on their own domains 3 g^j H_n: each chunk's full
+  // LDE on 3 H_2n (shift 3 / (3 g^j)), as quotient_slabs extends them.
+  void slab_chunks(int r) {
+    for (int k = 0; k < nc; k++) {
+      const int half = mc(k).p.chunks() / 2;
+      if (half <= r) continue;
+      const size_t n = hn[k];
+      const uint32_t g_inv = minv(two_adic_gen(log2i(n) + mc(k).p.log_quotient_degree()));
+      coset_lde(vals[k].p, n, 4, mpow(g_inv, (uint64_t)r), quotr.mats[qat[k] + r].lde.buf.p, st);
+      coset_lde(vals[k].p + 4 * n, n, 4, mpow(g_inv, (uint64_t)(r + half)),
+                quotr.mats[qat[k] + r + half].lde.buf.p, st);
+    }
+  }
+  // machine_time's form B: chip k's slab r alone, through a one-segment table.  The tables are
+  // built and uploaded once, ahead of the timed runs (chip_slab_setup), as quot_setup uploads the
+  // segmented form's: slab_chip is a launch and nothing else.
+  void chip_slab_setup() {
+    chip_slab_tab.clear();
+    chip_slab_tab.resize(3 * (size_t)nc);
+    for (int k = 0; k < nc; k++) {
+      const size_t n = hn[k];
+      const int mw = mc(k).p.lk.main_w, pw = mc(k).p.lk.prep_w;
+      for (int r = 1; r < mc(k).p.chunks() / 2; r++) {
+        QuotParams qp = qph[k];
+        slab_quot_params(qp, n, mc(k).p.log_quotient_degree(), r);
+        one_slab_table(chip_slab_tab[3 * k + r - 1], lists(k), slab[k].p,
+                       pw ? slab[k].p + 2 * n * (size_t)mw : nullptr,
+                       slab[k].p + 2 * n * (size_t)(mw + pw), log2i(n) + 1, qp,
+                       QuotOut{{vals[k].p, vals[k].p + 4 * n}, n}, st);
+      }
+    }
+  }
+  void slab_chip(int k, int r) { launch_slab_table(chip_slab_tab[3 * k + r - 1], lists(k).ncode > 0, st); }
   QuotOut quot_out(int k) {
-    return QuotOut{{quotr.mats[2 * k].lde.buf.p, quotr.mats[2 * k + 1].lde.buf.p + hn[k]}, 2 * hn[k]};
+    const int half = mc(k).p.chunks() / 2;
+    return QuotOut{{quotr.mats[qat[k]].lde.buf.p, quotr.mats[qat[k] + half].lde.buf.p + hn[k]}, 2 * hn[k]};
   }
   void quot_commit() {
     for (int k = 0; k < nc; k++)
-      for (int cc = 0; cc < 2; cc++) {  // the other half of each chunk LDE
-        CMat& qm = quotr.mats[2 * k + cc];
+      for (int cc = 0; cc < 2; cc++) {  // the other half of the LDEs of chunks 0 and D/2 (slab 0)
+        CMat& qm = quotr.mats[qat[k] + cc * (mc(k).p.chunks() / 2)];
         const uint32_t lde_shift = mmul(to_mont(3), minv(qm.shift));  // GENERATOR / shift
         coset_lde_ex(qm.lde.buf.p + (size_t)cc * hn[k], 2 * hn[k], hn[k], 4, lde_shift, qm.lde.buf.p,
                      1 - cc, st);
@@ -639,7 +850,7 @@ std::vector<uint8_t> machine_prove(const MachineProgram& m, const int* chips,
     for (int k = 0; k < nc; k++) mr.two.push_back(P.mc(k).local_only ? 0 : 1);
     oin.rounds.push_back(std::move(mr));
     oin.rounds.push_back(PcsRound{&P.permr, 1, std::vector<uint8_t>((size_t)nc, 1)});
-    oin.rounds.push_back(PcsRound{&P.quotr, 2, std::vector<uint8_t>(2 * (size_t)nc, 0)});
+    oin.rounds.push_back(PcsRound{&P.quotr, 2, std::vector<uint8_t>(P.quotr.mats.size(), 0)});
   }
   oin.zeta_d = zeta_d.p;  // (the unsharded plan reads zeta from the device alone)
   oin.observe_openings = opt.observe_openings;
@@ -684,9 +895,9 @@ std::vector<uint8_t> machine_prove(const MachineProgram& m, const int* chips,
     vals(mp[r0][k], 1, P.mc(k).p.lk.main_w);
     vals(mp[r0 + 1][k], 0, 4 * P.mc(k).p.perm_width());
     vals(mp[r0 + 1][k], 1, 4 * P.mc(k).p.perm_width());
-    w.u32(2);
-    vals(mp[r0 + 2][2 * k], 0, 4);
-    vals(mp[r0 + 2][2 * k + 1], 0, 4);
+    const int D = P.mc(k).p.chunks();  // 2 unless the chip's AIR has degree above 3
+    w.u32((uint32_t)D);
+    for (int j = 0; j < D; j++) vals(mp[r0 + 2][P.qat[k] + j], 0, 4);
     w.ef(P.cums[k]);
   }
   w.u32((uint32_t)po.commit_roots.size());
@@ -830,19 +1041,27 @@ void machine_time(const MachineProgram& m, const int* chips, const uint32_t* con
   P.perm_commit(/*tree=*/false);
   for (int k = 0; k < nc; k++) ch.observe_ef(P.cums[k]);
   P.quot_setup(ch.sample_ef());
+  P.chip_slab_setup();
   const uint32_t* twf = (const uint32_t*)twiddles().fwd();
   auto quot_loop = [&] {
     for (int k = 0; k < nc; k++)
       launch_quotient_chip_prog(P.lists(k), P.mainr.mats[k].lde.buf.p, P.prep_lde(k),
                                 P.permr.mats[k].lde.buf.p, log2i(P.hn[k]) + 1, P.qp_dev[k], twf,
                                 P.sel[k], P.quot_out(k), st);
+    for (int r = 1; r < P.max_half; r++) {  // the further slabs of the chips of degree above 3
+      P.slab_ldes(r);
+      for (int k = 0; k < nc; k++)
+        if (P.mc(k).p.chunks() / 2 > r) P.slab_chip(k, r);
+      P.slab_chunks(r);
+    }
   };
   std::vector<const uint32_t*> qsrc;
   std::vector<size_t> qwords;
-  for (int k = 0; k < 2 * nc; k++) {
-    qsrc.push_back(P.quotr.mats[k].lde.buf.p);
-    qwords.push_back(8 * P.hn[k / 2]);
-  }
+  for (int k = 0; k < nc; k++)
+    for (int j = 0; j < P.mc(k).p.chunks(); j++) {
+      qsrc.push_back(P.quotr.mats[P.qat[k] + j].lde.buf.p);
+      qwords.push_back(8 * P.hn[k]);
+    }
   clear(qsrc, qwords);  // (the halves the kernels do not write hold whatever the pool left there)
   for (int r = -1; r < runs; r++) {
     const float b = timed(quot_loop);
@@ -858,9 +1077,24 @@ void machine_time(const MachineProgram& m, const int* chips, const uint32_t* con
   }
 }
 
+// One chip's slab through the segmented kernel (chip_program.h; bfz_chip_quotient): a table of
+// one segment, built and uploaded by the call.
+void quotient_chip_slab(const ChipLists& cl, const uint32_t* mainc, const uint32_t* prepc,
+                        const uint32_t* permc, int logN, const QuotParams& slab_qp,
+                        const QuotOut& out, hipStream_t st) {
+  if (!cl.list || !mainc || !permc) throw std::runtime_error("chip program: null device argument");
+  if (logN < 1 || logN > 23) throw std::runtime_error("quotient_chip_slab: bad LDE height");
+  twiddles().ensure(logN);
+  DevTable dt;  // (freed stream-ordered after the launch)
+  one_slab_table(dt, cl, mainc, prepc, permc, logN, slab_qp, out, st);
+  launch_slab_table(dt, cl.ncode > 0 && cl.code, st);
+}
+
 // kernels a machine proof launches beside the built-in prover's (gpu.h PreloadKernels)
 static PreloadKernels preload_machine_program{(const void*)&k_quotient_machine<0>,
                                               (const void*)&k_quotient_machine<1>,
+                                              (const void*)&k_quotient_machine_coset<0>,
+                                              (const void*)&k_quotient_machine_coset<1>,
                                               (const void*)&k_perm_rows_machine<1>,
                                               (const void*)&k_check_machine<0>,
                                               (const void*)&k_check_machine<1>};

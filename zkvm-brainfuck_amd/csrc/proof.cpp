@@ -147,7 +147,7 @@ void read_opening_proof(In& r, ShardProof& pf) {
 // ------------------------------------------------------------------------------------ BFZ1
 namespace {
 // BFZ1 after the chip list: the roots, the opened values and the opening proof.
-ShardProof read_bfz1_body(In& r, ShardProof pf, size_t n) {
+ShardProof read_bfz1_body(In& r, ShardProof pf, size_t n, uint32_t max_chunks) {
   const uint32_t nc = (uint32_t)pf.chips.size();
   pf.main_root = r.digest();
   pf.perm_root = r.digest();
@@ -163,9 +163,10 @@ ShardProof read_bfz1_body(In& r, ShardProof pf, size_t n) {
     c.main_next = r.efs();
     c.perm_local = r.efs();
     c.perm_next = r.efs();
-    if (r.u32() != 2) throw std::runtime_error("bad quotient chunk count");
-    c.quotient[0] = r.efs();
-    c.quotient[1] = r.efs();
+    const uint32_t nq = r.u32();
+    if (nq < 2 || nq > max_chunks || (nq & (nq - 1))) throw std::runtime_error("bad quotient chunk count");
+    c.quotient.resize(nq);
+    for (std::vector<EF>& q : c.quotient) q = r.efs();
     c.cumsum = r.ef();
   }
   read_opening_proof(r, pf);
@@ -192,7 +193,7 @@ ShardProof decode_bfz1(const uint8_t* p, size_t n) {
     r.off += l;
     pf.chips.push_back((int)c);
   }
-  return read_bfz1_body(r, std::move(pf), n);
+  return read_bfz1_body(r, std::move(pf), n, 2);
 }
 
 ShardProof decode_bfz1_machine(const uint8_t* p, size_t n, const std::vector<std::string>& names) {
@@ -213,7 +214,7 @@ ShardProof decode_bfz1_machine(const uint8_t* p, size_t n, const std::vector<std
     r.off += l;
     pf.chips.push_back((int)c);
   }
-  return read_bfz1_body(r, std::move(pf), n);
+  return read_bfz1_body(r, std::move(pf), n, 8);
 }
 
 // ------------------------------------------------------------------------------------ BFU1
@@ -278,9 +279,8 @@ std::vector<uint8_t> encode_bfz1(const ShardProof& pf) {
     w.efs(c.main_next);
     w.efs(c.perm_local);
     w.efs(c.perm_next);
-    w.u32(2);
-    w.efs(c.quotient[0]);
-    w.efs(c.quotient[1]);
+    w.u32((uint32_t)c.quotient.size());
+    for (const std::vector<EF>& q : c.quotient) w.efs(q);
     w.ef(c.cumsum);
   }
   w.digests(pf.commit_roots);
@@ -324,9 +324,8 @@ std::vector<uint8_t> encode_bincode(const ShardProof& pf, FieldRepr repr) {
     w.efs(c.main_next);
     w.efs(c.perm_local);
     w.efs(c.perm_next);
-    w.len(2);             // quotient: Vec<Vec<Challenge>>
-    w.efs(c.quotient[0]);
-    w.efs(c.quotient[1]);
+    w.len(c.quotient.size());  // quotient: Vec<Vec<Challenge>>
+    for (const std::vector<EF>& q : c.quotient) w.efs(q);
     w.ef(c.cumsum);       // cumulative_sum: Challenge = [Val; 4], no length
     w.u64(c.log_degree);  // log_degree: usize
   }
@@ -378,8 +377,7 @@ ShardProof decode_bincode(const uint8_t* p, size_t n, FieldRepr repr) {
     c.perm_local = r.efs();
     c.perm_next = r.efs();
     if (r.len(8) != 2) throw std::runtime_error("bad quotient chunk count");
-    c.quotient[0] = r.efs();
-    c.quotient[1] = r.efs();
+    c.quotient = {r.efs(), r.efs()};
     c.cumsum = r.ef();
     const uint64_t lg = r.u64();
     if (lg > 64) throw std::runtime_error("log degree out of range");

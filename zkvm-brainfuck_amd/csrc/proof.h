@@ -26,7 +26,8 @@ struct ChipOpened {                  // ChipOpenedValues<Challenge> (types.rs:44
   int chip = 0;                      // index in BfAir::chips() order (machine.h Chip)
   uint32_t log_degree = 0;
   std::vector<EF> prep_local, prep_next, main_local, main_next, perm_local, perm_next;
-  std::vector<EF> quotient[2];       // quotient chunks opened at zeta (4 EF each)
+  // quotient chunks opened at zeta (4 EF each): 2, or 2^lqd of a machine's chip program
+  std::vector<std::vector<EF>> quotient;
   EF cumsum{};
 };
 
@@ -82,7 +83,8 @@ ShardProof decode_bfz1(const uint8_t* p, size_t n);   // throws on malformed inp
 // chip's index in the machine's list (names[index] must follow it), up to names.size() chips.  A
 // machine without preprocessed columns commits no preprocessed round, so each of its queries
 // lists three input rounds (main, permutation, quotient); the count of input rounds is a length
-// word of the query encoding, so the four-round bytes are what they were.
+// word of the query encoding, so the four-round bytes are what they were.  A chip's chunk count
+// word is 2, 4 or 8; whether it is the chip's own count is machine_verify's shape check.
 ShardProof decode_bfz1_machine(const uint8_t* p, size_t n, const std::vector<std::string>& names);
 std::vector<uint8_t> encode_bfz1(const ShardProof& pf);
 ShardProof decode_bincode(const uint8_t* p, size_t n, FieldRepr repr);

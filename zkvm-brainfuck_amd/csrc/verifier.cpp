@@ -250,8 +250,9 @@ void before_queries(const std::string& src, const uint32_t vk_commit[8], const S
       // log degree 0 is a 1-row trace (the Cpu chip of a one-cycle program: cpu/trace.rs:33
       // pads to next_power_of_two with no minimum)
       if (o.log_degree > 23) throw std::runtime_error("log degree out of range");
+      if (o.quotient.size() != 2) throw std::runtime_error("opened-value shape mismatch");
       co.push_back(ChipOpen{(int)o.log_degree, o.prep_local, o.prep_next, o.main_local, o.main_next,
-                            o.perm_local, o.perm_next, o.quotient, o.cumsum});
+                            o.perm_local, o.perm_next, o.quotient.data(), o.cumsum});
       const ChipOpen& c = co.back();
       const int ch = chip[i];
       const size_t pw = CHIP_INFO[ch].prep_w;
@@ -1179,15 +1180,26 @@ void machine_before_queries(const MachineProgram& m, Challenger& ch, const uint8
   for (uint32_t i = 0; i < nc; i++) {
     const ChipOpened& ov = pf.opened[i];
     const MachineChip& mc = m.chips[chip[i]];
-    if (ov.log_degree > 23) throw std::runtime_error("log degree out of range");
+    try {  // a program compiled under a higher cap than the one in force
+      chip_cap_or_throw(mc.p);
+    } catch (const std::exception& e) {
+      throw std::runtime_error("machine: chip " + mc.name + ": " + e.what());
+    }
+    // the quotient domain 3 H_(D n) must exist (two-adicity 24); D = 2: every height up to 2^23
+    const int lqd = mc.p.log_quotient_degree();
+    if (ov.log_degree > 23 || (lqd > 1 && ov.log_degree + (uint32_t)lqd > 24))
+      throw std::runtime_error("log degree out of range");
+    if (ov.quotient.size() != (size_t)mc.p.chunks()) throw std::runtime_error("opened-value shape mismatch");
     co.push_back(ChipOpen{(int)ov.log_degree, ov.prep_local, ov.prep_next, ov.main_local,
-                          ov.main_next, ov.perm_local, ov.perm_next, ov.quotient, ov.cumsum});
+                          ov.main_next, ov.perm_local, ov.perm_next, ov.quotient.data(), ov.cumsum});
     const ChipOpen& c = co.back();
     const size_t pw = (size_t)mc.p.lk.prep_w;
     if (c.ml.size() != (size_t)mc.p.lk.main_w || c.mn.size() != c.ml.size() ||
         c.perml.size() != 4 * (size_t)mc.p.perm_width() || c.permn.size() != c.perml.size() ||
-        c.pl.size() != pw || c.pn.size() != pw || c.q[0].size() != 4 || c.q[1].size() != 4)
+        c.pl.size() != pw || c.pn.size() != pw)
       throw std::runtime_error("opened-value shape mismatch");
+    for (const std::vector<EF>& q : ov.quotient)
+      if (q.size() != 4) throw std::runtime_error("opened-value shape mismatch");
     if (mc.local_only)  // (as before_queries: the prover's zeros are required)
       for (const std::vector<EF>* v : {&c.pn, &c.mn})
         for (const EF& e : *v)
@@ -1227,10 +1239,12 @@ void machine_before_queries(const MachineProgram& m, Challenger& ch, const uint8
     S.rounds[r].push_back(VMat{c.log_n, ONE, (int)c.ml.size(), m.chips[chip[i]].local_only ? 1 : 2,
                                {zeta, znext}, {&c.ml, &c.mn}});
     S.rounds[r + 1].push_back(VMat{c.log_n, ONE, (int)c.perml.size(), 2, {zeta, znext}, {&c.perml, &c.permn}});
-    const uint32_t w2n = two_adic_gen(c.log_n + 1);
-    for (int k = 0; k < 2; k++)
-      S.rounds[r + 2].push_back(VMat{c.log_n, mmul(to_mont(3), k ? w2n : ONE), 4, 1, {zeta, zeta},
-                                     {&c.q[k], &c.q[k]}});
+    // split_domains: chunk j of the chip's D on 3 w_(D n)^j H_n
+    const int D = m.chips[chip[i]].p.chunks();
+    const uint32_t wq = two_adic_gen(c.log_n + m.chips[chip[i]].p.log_quotient_degree());
+    for (int k = 0; k < D; k++)
+      S.rounds[r + 2].push_back(VMat{c.log_n, mmul(to_mont(3), mpow(wq, (uint64_t)k)), 4, 1,
+                                     {zeta, zeta}, {&c.q[k], &c.q[k]}});
   }
   S.roots[r] = pf.main_root.data();
   S.roots[r + 1] = pf.perm_root.data();
@@ -1255,12 +1269,16 @@ void machine_before_queries(const MachineProgram& m, Challenger& ch, const uint8
     const ChipOpen& c = co[i];
     const MachineChip& mc = m.chips[chip[i]];
     const int n_log = c.log_n;
-    const uint32_t w2n = two_adic_gen(n_log + 1);
-    const uint32_t sh[2] = {to_mont(3), mmul(to_mont(3), w2n)};
+    const int D = mc.p.chunks();  // the chunks recomposed as uni_after_queries recomposes them
+    const uint32_t wq = two_adic_gen(n_log + mc.p.log_quotient_degree());
+    std::vector<uint32_t> sh((size_t)D);
+    for (int a = 0; a < D; a++) sh[a] = mmul(to_mont(3), mpow(wq, (uint64_t)a));
     EF quot = ef_zero();
-    for (int a = 0; a < 2; a++) {
-      const int b = 1 - a;
-      const EF zps = ef_mul(zp_at(n_log, sh[b], zeta), ef_inv(zp_at(n_log, sh[b], ef_base(sh[a]))));
+    for (int a = 0; a < D; a++) {
+      EF zps = ef_one();
+      for (int b = 0; b < D; b++)
+        if (b != a)
+          zps = ef_mul(zps, ef_mul(zp_at(n_log, sh[b], zeta), ef_inv(zp_at(n_log, sh[b], ef_base(sh[a])))));
       for (int e = 0; e < 4; e++) quot = ef_add(quot, ef_mul(ef_mul(zps, monomial(e)), c.q[a][e]));
     }
     const uint32_t gn_inv = minv(two_adic_gen(n_log));
